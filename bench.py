@@ -21,6 +21,17 @@ its own key range with no data-path collective (weak scaling). Launch: python be
 --warmup W]; for N > 1 under torch.distributed.run (one rank per GPU; WORLD_SIZE must equal N), or without a
 launcher, in which case bench.py starts torch.distributed.run with N ranks itself (launch_command).
 
+A plain run does only what the headline figure needs: it generates the stream, warms up, times the K steps and prints
+the result line (with the per-kernel marks the library records during those same steps). `--full` adds the side lines
+that take runs of their own: the CPU baseline (oracle/cpu_ref, one thread and all host threads), the end-to-end
+variant with H2D, the sparse 64-bit key variant and the input-handler variant; `--no-cpu`, `--no-e2e`, `--no-sparse`
+and `--no-ih` drop single ones from a full run. `--dump-outputs DIR` writes, after the timed steps, what the last
+timed step handed its caller as DIR/<name>.npy (float64): the (e1, e2) ordinals of every match tuple in output order
+(configs 3 and 4), the kept rows (config 2) or the output records (config 5). An output over the 64 MB budget is
+written as a fixed sample: the rows at <name>_index.npy (seeded, sorted), with the full row count in
+<name>_count.npy. The stream is counter-based (splitmix64 of a fixed seed), so two runs with the same arguments
+see identical inputs and their dumps compare output for output.
+
 The other §8(d) configurations are parity/measurement side lines, selected with --config:
   --config 2   filter-only `StockStream[price > 70 and volume < 1000]`, N = 1e9 (bandwidth roofline);
                multi-GPU: contiguous index ranges per rank, no exchange (strong scaling)
@@ -285,6 +296,49 @@ def log(*a):
     print("[bench]", *a, file=sys.stderr, flush=True)
 
 
+DUMP_BUDGET = 64_000_000  # --dump-outputs: bytes over all files of one run (4096 of them kept for the .npy headers)
+DUMP_SEED = 0x0D0E5EED   # of the sampled row indices
+
+
+def sample_rows(n, width):
+    """--dump-outputs: the rows of an (n, width) output that are written. None = all of them; otherwise as many as fit
+    the budget as float64 next to their own float64 indices, drawn by a seeded host generator and sorted (the same rows
+    for the same n)."""
+    import torch
+    fit = (DUMP_BUDGET - 4096) // (8 * (width + 1))
+    if n <= fit:
+        return None
+    g = torch.Generator()
+    g.manual_seed(DUMP_SEED)
+    return torch.randint(0, n, (fit,), generator=g).sort().values
+
+
+def write_outputs(dirname, name, t, packed, suffix=""):
+    """--dump-outputs: the integer device tensor `t` of n rows as <dirname>/<name><suffix>.npy in float64 (ordinals,
+    event times and counts, all far below 2^53), whole or as sample_rows' sample (then with <name>_index), and the
+    row count as <name>_count. packed: every row is one match tuple (e2 << 32) | e1, written as the columns e1, e2."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    t = t.reshape(t.shape[0], -1)
+    n = t.shape[0]
+    idx = sample_rows(n, 2 if packed else t.shape[1])
+    rows = (t if idx is None else t[idx.to(t.device)]).cpu()
+    if packed:
+        rows = torch.cat([rows & 0xFFFFFFFF, (rows >> 32) & 0xFFFFFFFF], dim=1)
+    files = {name: rows.numpy(), name + "_count": np.array([n])}
+    if idx is not None:
+        files[name + "_index"] = idx.numpy()
+    total = 0
+    for fn, a in files.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        total += a.nbytes + 128  # the .npy header
+        np.save(os.path.join(dirname, fn + suffix + ".npy"), a)
+    if total > DUMP_BUDGET:
+        raise RuntimeError(f"--dump-outputs wrote {total} bytes, over the {DUMP_BUDGET} budget")
+    log(f"wrote {name}{suffix}: {rows.shape[0]} of {n} rows to {dirname}")
+
+
 # Per configuration: app, default N, event-time divisor, whether the path shards, whole-job algorithmic bytes
 # (SURVEY.md §8(d)) and the kernels of its device pipeline.
 CONFIGS = {
@@ -443,6 +497,12 @@ def build_parser():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side lines that take runs of their own: CPU baseline, end-to-end (H2D) variant, "
+                         "sparse-key variant, input-handler variant")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float64, at most "
+                         "64 MB: a fixed seeded sample of a larger output)")
     ap.add_argument("--config", type=int, default=4, choices=sorted(CONFIGS))
     ap.add_argument("--events", type=float, default=None)
     ap.add_argument("--keys", type=int, default=1_000_000)
@@ -477,6 +537,10 @@ def build_parser():
 def main():
     ap = build_parser()
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.via_input_handler and not args.full:
+        ap.error("--via-input-handler sizes the input-handler variant, which runs with --full")
     # before anything touches the GPU: N > 1 without a launcher starts one (a child process, never an exec)
     cmd = launch_command(args.gpus, sys.argv[1:], os.environ)
     if cmd is not None:
@@ -556,7 +620,7 @@ def main():
     # records of the last step, this rank's part of the delivery order, to <prefix>.rank<r>.pt (outside the timing)
     dump = os.environ.get("SM_BENCH_DUMP") if args.config == 5 else None
     last_recs = [None]
-    if args.config == 5 and (world > 1 or dump):
+    if args.config == 5 and (world > 1 or dump or args.dump_outputs):
         opts["keep_outputs"] = 1  # the output records of each batch stay on the device for the cross-rank merge
     if args.heap_words:
         opts["heap_words"] = args.heap_words
@@ -589,8 +653,7 @@ def main():
                 # rank that ingested its trigger, ordered there (timers of one clock advance in key creation order)
                 merged = merge_outputs(app.copy_device_outputs("q"), starts, N, world)
                 out_local[0] = merged.shape[0]
-                if dump:
-                    last_recs[0] = merged
+                last_recs[0] = merged
             elif dump:
                 last_recs[0] = app.copy_device_outputs("q")
             return int(app.get_stat("output_events:q"))
@@ -618,6 +681,7 @@ def main():
             mine = partitioned_step(symbol, [symbol, price, ts], world, lo, N, match, starts=starts, offsets=offsets)
             if mine is not None:
                 out_local[0] = mine.numel()
+                last_recs[0] = mine
             return nm[0]
         s_sym, s_price, s_ts, s_ord = symbol, price, ts, None
         n_local[0] = s_ts.numel()
@@ -631,8 +695,27 @@ def main():
             if mbuf[0] is None or mbuf[0].numel() < m:
                 mbuf[0] = torch.empty(max(m, 1) + (m >> 3), dtype=torch.int32, device=dev)
             app.copy_device_matches("q", mbuf[0])
-            out_local[0] = concat_ordered(mbuf[0][:m].to(torch.int64) + lo, world).numel()
+            last_recs[0] = concat_ordered(mbuf[0][:m].to(torch.int64) + lo, world)
+            out_local[0] = last_recs[0].numel()
         return m
+
+    def last_outputs():
+        """--dump-outputs: what the last step handed its caller, as (name, integer device tensor, packed). One rank
+        reads the library's device buffer (match tuples packed (e2 << 32) | e1, a filter's kept rows, or config 5's
+        output records: sm_out_rec + select values + ordinals as int64 words); a rank of several kept what it received
+        in the step (last_recs)."""
+        name = {2: "rows", 5: "records"}.get(args.config, "matches")
+        if world > 1 and shards:
+            t = last_recs[0]
+        elif args.config == 5:
+            t = app.copy_device_outputs("q")
+        else:
+            m = app.device_matches("q")[1]
+            t = torch.empty(max(m, 1), dtype=torch.int32 if args.config == 2 else torch.int64, device=dev)
+            app.copy_device_matches("q", t)
+            torch.cuda.synchronize()
+            t = t[:m]
+        return name, t, args.config in (3, 4)
 
     log(f"rank {rank}: config {args.config}, {hi - lo} events resident; warmup {args.warmup}")
     for _ in range(args.warmup):
@@ -661,6 +744,8 @@ def main():
     dt = time.perf_counter() - t0
     if dump and last_recs[0] is not None:
         torch.save(last_recs[0].cpu(), f"{dump}.rank{rank}.pt")
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, *last_outputs(), suffix=f".rank{rank}" if world > 1 else "")
     path = app.get_stat("fast_path:q")
     nfa_kernel = int(app.get_stat("nfa_kernel:q")) if args.config == 5 else 0
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -682,7 +767,7 @@ def main():
     build_id = _lib.lib().sm_build_id().decode()
     roof = roofline(ktot, n_local[0], nm, args.steps, args.config, build_id, args.variant)
     e2e = None
-    if args.config == 4 and world == 1 and not args.no_e2e:
+    if args.full and args.config == 4 and world == 1 and not args.no_e2e:
         # SURVEY.md §8(d) end-to-end variant: the same step with the three columns the plan reads (symbol i32,
         # price f64, event time i64: 20 B/event) copied host -> device first, from pinned host buffers, timed together
         log("e2e variant: pinning the host columns")
@@ -708,7 +793,7 @@ def main():
                "note": "H2D of symbol + price + event time from pinned host memory over PCIe, then the step; "
                        "not overlapped (best of 2)"}
     sparse = None
-    if args.config == 4 and world == 1 and not args.no_sparse:
+    if args.full and args.config == 4 and world == 1 and not args.no_sparse:
         # the same stream keyed by sparse 64-bit ids (splitmix64 of the dense symbol: K ids over the whole int64
         # range), `symbol long`: the keys become dense ids on the device (remap_keys) before key pass 0
         log("sparse-key variant")
@@ -737,7 +822,7 @@ def main():
         app_s.close()
         del key64
     ih = None
-    if args.config in (3, 4) and world == 1 and not args.no_ih:
+    if args.full and args.config in (3, 4) and world == 1 and not args.no_ih:
         n_ih = N if args.via_input_handler else min(N, int(args.ih_events))
         log(f"input-handler variant on {n_ih} events")
         app.set_option("reset", 0)
@@ -750,7 +835,7 @@ def main():
         ih = via_input_handler([symbol, price, vol_attr, tsattr, ts], n_ih, expect,
                                int(args.ih_chunk) if args.ih_chunk else None, cfg["app"])
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         sample = args.cpu_sample or cfg["cpu_sample"]
         log(f"cpu baseline on {sample} events")
         v, sec, mm = cpu_baseline(sample, K, ts_div, cfg["app"], seed, cfg["out"], args.config)
@@ -792,6 +877,7 @@ def main():
         line = {
             "metric": METRIC if args.config == 4 else f"input events/sec + % HBM peak, {cfg['workload']}",
             "value": value, "unit": "events/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": ms_per_step, "higher_is_better": True,
             "scaling": plan["scaling"], "vs_baseline": None,
             "dtype": "f64", "data": "synthetic (counter-based splitmix64 StockStream, device-resident)",

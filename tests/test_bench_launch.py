@@ -3,7 +3,8 @@ processes itself; under a launcher whose WORLD_SIZE differs from N it fails inst
 multi-rank config-4 step (shard.partitioned_step, the code bench.py runs over RCCL) is checked here on CPU with gloo
 at world 2: the ranks' outputs in rank order equal the world-1 output, on bench.py's own synthetic stream. The
 per-rank matcher is the CPU oracle (this checks the sharding of the step; the kernels are checked in the -m gpu
-tests)."""
+tests). Also here: a plain run carries no side line, `--full` keeps them all, and `--dump-outputs` writes the last
+step's outputs (whole, or the same seeded sample on every run)."""
 import ctypes
 import json
 import os
@@ -159,3 +160,86 @@ def test_stale_pmc_profile_yields_null_traffic(tmp_path, monkeypatch):
     doc["variant"] = "pattern_count_not5s"
     (tmp_path / "profiles" / "pmc_config4_pattern_count_not5s.json").write_text(json.dumps(doc))
     assert bench.roofline(ktot, n, m, 5, 4, build_id="abcd", variant="pattern_count_not5s")["traffic"] == 5e4
+
+
+def test_plain_run_is_the_default_and_full_is_opt_in():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times its steps only; the side lines that take runs of their
+    own (CPU baseline, H2D, sparse keys, input handler) wait for --full."""
+    ap = bench.build_parser()
+    plain = ap.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not plain.full and plain.dump_outputs is None and plain.steps == 3 and plain.warmup == 1
+    full = ap.parse_args(["--full", "--dump-outputs", "d"])
+    assert full.full and full.dump_outputs == "d"
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: float64 .npy files; packed tuples become (e1, e2) columns; an output over the 64 MB budget is
+    written as the same seeded, sorted sample of rows on every run, with its row indices and the full row count."""
+    e1 = torch.arange(10, dtype=torch.int64) + 100
+    e2 = torch.arange(10, dtype=torch.int64) + 3_000_000_000  # above 2^31: the high word is read unsigned
+    d = str(tmp_path / "small")
+    bench.write_outputs(d, "matches", (e2 << 32) | e1, True)
+    got = np.load(os.path.join(d, "matches.npy"))
+    assert got.dtype == np.float64 and got.shape == (10, 2)
+    np.testing.assert_array_equal(got, np.stack([e1.numpy(), e2.numpy()], axis=1))
+    assert np.load(os.path.join(d, "matches_count.npy")).tolist() == [10]
+    assert not os.path.exists(os.path.join(d, "matches_index.npy"))
+    bench.write_outputs(d, "records", torch.arange(60, dtype=torch.int64).reshape(5, 12), False, suffix=".rank1")
+    assert np.load(os.path.join(d, "records.rank1.npy")).shape == (5, 12)
+
+    n = 3_000_000  # 48 MB of (e1, e2) + nothing else would fit; with the indices it does not
+    big = (torch.arange(n, dtype=torch.int64) << 32) | 7
+    dirs = [str(tmp_path / x) for x in "ab"]
+    for x in dirs:
+        bench.write_outputs(x, "matches", big, True)
+    files = sorted(os.listdir(dirs[0]))
+    assert files == ["matches.npy", "matches_count.npy", "matches_index.npy"]
+    assert sum(os.path.getsize(os.path.join(dirs[0], f)) for f in files) <= 64_000_000
+    a = {f: np.load(os.path.join(dirs[0], f)) for f in files}
+    for f in files:
+        np.testing.assert_array_equal(a[f], np.load(os.path.join(dirs[1], f)))
+    idx = a["matches_index.npy"]
+    assert a["matches_count.npy"].tolist() == [n] and 2_000_000 < idx.size < n
+    assert (np.diff(idx) >= 0).all() and idx[0] >= 0 and idx[-1] < n
+    np.testing.assert_array_equal(a["matches.npy"], np.stack([np.full(idx.size, 7.0), idx], axis=1))
+
+
+def _bench_line(extra, timeout=280):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--events", str(N), "--keys",
+                        str(K), "--ts-div", str(DIV), "--steps", "2", "--warmup", "1"] + extra, env=_env(),
+                       capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0, r.stderr[-3000:]
+    js = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
+    assert len(js) == 1
+    return js[0]
+
+
+SIDE_LINES = ("e2e_with_h2d", "via_input_handler", "sparse_keys")
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_plain_bench_dumps_the_oracle_matches(tmp_path):
+    """The plain run on the small stream of this file: the headline fields, no side line, and --dump-outputs holding
+    the last step's match tuples, which are the CPU oracle's for the same stream, in its order."""
+    d = str(tmp_path / "out")
+    line = _bench_line(["--dump-outputs", d])
+    assert line["steps"] == 2 and line["warmup"] == 1 and not line["full"]
+    assert line["unit"] == "events/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert abs(line["value"] - N / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    assert line["cpu_baseline"] is None and not any(k in line for k in SIDE_LINES)
+    sym, price, vol, tsa, ts = bench.gen_stock(0, N, K, DIV, torch.device("cpu"), bench.seed_for(4))
+    want = oracle_match([sym, price, ts], None).numpy()
+    got = np.load(os.path.join(d, "matches.npy"))
+    assert got.dtype == np.float64 and sorted(os.listdir(d)) == ["matches.npy", "matches_count.npy"]
+    assert line["config"]["matches"] == len(want) == got.shape[0] > 0.3 * N
+    np.testing.assert_array_equal(got, np.stack([want & 0xFFFFFFFF, want >> 32], axis=1))
+
+
+@pytest.mark.gpu
+@pytest.mark.timeout(300)
+def test_full_bench_keeps_its_side_lines():
+    line = _bench_line(["--full", "--cpu-sample", "20000"])
+    assert line["full"] and all(line[k]["value"] > 0 for k in SIDE_LINES)
+    assert line["cpu_baseline"]["value"] > 0 and "oracle/cpu_ref" in line["cpu_baseline"]["sample"]
+    assert line["via_input_handler"]["output_events"] == line["config"]["matches"] > 0

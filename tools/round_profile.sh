@@ -21,7 +21,7 @@ step() {  # step <name> <seconds> <cmd...>
   return 0
 }
 cd "$ROOT"
-step bench_full 600 python -u bench.py "$@"
+step bench_full 600 python -u bench.py --full "$@"
 cd /tmp
 step prof_stats 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_stats" -o run -- \
   python3 "$ROOT/bench.py" --no-cpu --no-e2e --no-ih --no-sparse --steps 3 --warmup 1 "$@"
