@@ -400,39 +400,51 @@ struct OrigSrc {
     r.w = (uint32_t)(ts[p] - ts0);
     return r;
   }
-  // raw column values of one event (loads in flight until split() uses them) + its c1 mask word
+  // raw column values of one event (loads in flight until split() / record() use them). Only what the record keeps:
+  // the record holds key - kmin, ts - ts0, the relative ordinal and one c1 bit, all mod 2^32 or less, so the low 32
+  // bits of the key, the timestamp and the ordinal and the 32-bit half of the c1 mask word with the event's bit are
+  // loaded (the same cache lines; 3 VGPRs an event where the whole timestamp, ordinal and mask words took 6). o is
+  // the ordinal as loaded: obase is subtracted where it is used, so that load() itself needs no loaded value and a
+  // tile's loads all issue before the first wait. o without an ordinal column and m with c1 evaluated inline are
+  // left unset and never read: a constant moved into a register that a load of the tile before also wrote would be
+  // a vmcnt wait inside load().
   struct Raw {
-    KT k;
+    uint32_t k;
     VT v;
-    int64_t t, o;
-    uint64_t m;
+    uint32_t t, o, m;
   };
   __device__ Raw load(int64_t p) const {
     Raw r;
+    const uint32_t* t32 = (const uint32_t*)(ts + p);  // little endian: the low half first
 #if SM_ORIG_NT_LOAD
     // read-once columns: nontemporal loads keep the L2 for the pass's scattered record stores (as RecSrc)
-    r.k = __builtin_nontemporal_load(kcol + p);
+    r.k = __builtin_nontemporal_load((const uint32_t*)(kcol + p));
     r.v = __builtin_nontemporal_load(vcol + p);
-    r.t = __builtin_nontemporal_load(ts + p);
-    r.o = ord ? __builtin_nontemporal_load(ord + p) - obase : p;
+    r.t = __builtin_nontemporal_load(t32);
+    if (ord) r.o = __builtin_nontemporal_load((const uint32_t*)(ord + p));
 #else
-    r.k = kcol[p];
+    r.k = *(const uint32_t*)(kcol + p);
     r.v = vcol[p];
-    r.t = ts[p];
-    r.o = ord ? ord[p] - obase : p;
+    r.t = *t32;
+    if (ord) r.o = *(const uint32_t*)(ord + p);
 #endif
-    r.m = c1_inline ? 0ull : c1mask[p >> 6];
+    if (!c1_inline) r.m = ((const uint32_t*)c1mask)[p >> 5];
     return r;
   }
+  __device__ uint32_t rel_ord(const Raw& r, int64_t p) const { return ord ? r.o - (uint32_t)obase : (uint32_t)p; }
+  __device__ uint32_t c1_of(const Raw& r, int64_t p) const {
+    if (c1_inline) return eval_simple(c1, ValLoader<VT>{r.v}) ? 1u : 0u;
+    return (r.m >> (p & 31)) & 1u;
+  }
   __device__ void split(const Raw& r, int64_t p, uint64_t& a, uint64_t& b) const {
-    const uint32_t c1 = c1_bit(r.v, r.m, p);
-    a = (uint64_t)((uint32_t)((int64_t)r.k - kmin) | (c1 << 31)) | ((uint64_t)(uint32_t)r.o << 32);
-    b = (uint64_t)vcode<VT>(r.v, vmode, vmin) | ((uint64_t)(uint32_t)(r.t - ts0) << 32);
+    const uint32_t c1 = c1_of(r, p);
+    a = (uint64_t)((r.k - (uint32_t)kmin) | (c1 << 31)) | ((uint64_t)rel_ord(r, p) << 32);
+    b = (uint64_t)vcode<VT>(r.v, vmode, vmin) | ((uint64_t)(r.t - (uint32_t)ts0) << 32);
   }
   __device__ uint4 record(const Raw& r, int64_t p) const {  // pass0_kernel (pass0_dev.h)
-    const uint32_t c1 = c1_bit(r.v, r.m, p);
-    return make_uint4((uint32_t)((int64_t)r.k - kmin) | (c1 << 31), (uint32_t)r.o, vcode<VT>(r.v, vmode, vmin),
-                      (uint32_t)(r.t - ts0));
+    const uint32_t c1 = c1_of(r, p);
+    return make_uint4((r.k - (uint32_t)kmin) | (c1 << 31), rel_ord(r, p), vcode<VT>(r.v, vmode, vmin),
+                      r.t - (uint32_t)ts0);
   }
   __device__ void flush() {}
 };

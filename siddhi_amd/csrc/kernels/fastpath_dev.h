@@ -97,6 +97,25 @@ __device__ __forceinline__ uint64_t lanemask_lt() {
   return lane == 0 ? 0ull : (~0ull >> (64 - lane));
 }
 
+// set bits of m below this lane (m & lanemask_lt(), counted): mbcnt needs no lane mask in registers
+__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+#else
+  return (uint32_t)__popcll(m & lanemask_lt());
+#endif
+}
+
+// The wave's index in its workgroup as a scalar: what depends on it alone (masks over the waves before this one,
+// the wave's first record of a tile) then lives in SGPRs and not in one VGPR per value per lane.
+__device__ __forceinline__ int wave_index() {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+#else
+  return (int)(threadIdx.x >> 6);
+#endif
+}
+
 __device__ __forceinline__ StackVal col_value(const NfaStream* st, int a, int64_t row) {
   StackVal v;
   v.i = 0;

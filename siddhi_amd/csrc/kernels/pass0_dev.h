@@ -63,6 +63,28 @@ __device__ __forceinline__ uint32_t p0_before(const uint4& r0, const uint4& r1, 
   return s;
 }
 
+// Scheduling fence between the build of the next tile's records and the tile's global stores: the records (and so
+// the wait for their loads) are complete before it, and no memory operation moves across it. No instruction.
+__device__ __forceinline__ void p0_store_fence(uint4 (&rec)[kP0Items]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+  for (int k = 0; k < kP0Items; ++k)
+    asm volatile("" : "+v"(rec[k].x), "+v"(rec[k].y), "+v"(rec[k].z), "+v"(rec[k].w) : : "memory");
+#else
+  (void)rec;
+#endif
+}
+
+// A wave-uniform value the optimiser cannot see through (an SGPR pair). The tile base passes through it before the
+// column addresses are formed: otherwise loop strength reduction keeps one 64-bit pointer per column and item alive
+// across the whole loop (40 VGPRs), which the pipelined loop cannot afford. No instruction.
+__device__ __forceinline__ int64_t p0_opaque(int64_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+s"(v));
+#endif
+  return v;
+}
+
 // Chunk blockIdx.x = [blockIdx.x * per, + per) of the batch, tile by tile. cnt[d * G + g] = records of digit d in
 // chunks before g (scan_chunks), dbase[d] = records of digits before d: chunk g's first position for digit d is
 // dbase[d] + cnt[d * G + g].
@@ -78,8 +100,7 @@ __global__ void __launch_bounds__(kP0Block) pass0_kernel(Src src, uint4* __restr
   __shared__ __attribute__((aligned(16))) uint4 carry[kBins][kP0Seg - 1];
   __shared__ uint32_t lw[kP0Waves];
 
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const uint64_t lt = lanemask_lt();
+  const int tid = threadIdx.x, lane = tid & 63, w = wave_index();
   const int64_t lo = (int64_t)blockIdx.x * per;
   int64_t len = n - lo;
   if (len > per) len = per;
@@ -99,27 +120,78 @@ __global__ void __launch_bounds__(kP0Block) pass0_kernel(Src src, uint4* __restr
   auto load_tile = [&](int64_t base) {
     const int64_t rem = lo + len - base;
     const int tn = rem < kP0Tile ? (int)rem : kP0Tile;
+    base = p0_opaque(base);
 #pragma unroll
     for (int k = 0; k < kP0Items; ++k) {
       const int e = w * 64 * kP0Items + k * 64 + lane;
       if (e < tn) raw[k] = src.load(base + e);
     }
   };
+  // Software pipeline. gfx9 counts vector loads and stores in one in-order vmcnt, so a wait for a load that was
+  // issued after a store also waits for that store's acknowledgement. Hence the order: tile t's column loads are
+  // issued inside tile t-1 (after its ranking), and src.record consumes them after tile t-1's placement barrier and
+  // BEFORE tile t-1's global stores. That wait is the loop's only one for vector memory, and the youngest stores it
+  // has behind it are tile t-2's, a whole tile old; tile t-1's scattered stores drain during tile t's ranking and
+  // scan. The loop is rotated so that each stage has one site: an iteration builds the records of the tile at
+  // `base` (if there is one), stores the tile before it (if there is one), then ranks, scans and places its own.
+  const int64_t end = lo + len;
   if (len > 0) load_tile(lo);
+  // the placed, not yet stored tile: its size, whether it ends the chunk
+  int ptile_n = 0;
+  bool plast = false;
+  uint4 cq0, cq1, cq2;  // digit tid's carried records that leave with that tile
+  static_assert(kP0Seg == 4, "three carried records at most");
 
-  for (int64_t base = lo; base < lo + len; base += kP0Tile) {
-    const int tile_n = (int)((lo + len - base) < kP0Tile ? (lo + len - base) : kP0Tile);
-    const bool last = base + kP0Tile >= lo + len;
+  for (int64_t base = lo;; base += kP0Tile) {
+    const bool more = base < end;
+    const int tile_n = (int)((end - base) < kP0Tile ? (end - base) : kP0Tile);
+    const bool last = base + kP0Tile >= end;
     uint4 rec[kP0Items];
+    if (more) {  // the loop's only wait for vector memory
 #pragma unroll
-    for (int k = 0; k < kP0Items; ++k) {
-      const int e = w * 64 * kP0Items + k * 64 + lane;
-      if (e < tile_n) rec[k] = src.record(raw[k], base + e);
+      for (int k = 0; k < kP0Items; ++k) {
+        const int e = w * 64 * kP0Items + k * 64 + lane;
+        if (e < tile_n) rec[k] = src.record(raw[k], base + e);
+      }
     }
-    // (the previous tile's readers of xb / tstart / run / cst / carry finished before its closing barrier)
+    p0_store_fence(rec);
+
+    if (base != lo) {  // the tile before: its leaving carried records, then its own
+      // digit tid's run / carry start / tile count, unchanged in LDS since that tile's scan (kept in no register
+      // across the record build)
+      const uint32_t rn = run[tid], c0 = cst[tid], ct = tstart[tid + 1] - tstart[tid];
+      const uint32_t lim = plast ? 0xffffffffu : ((rn + ct) & ~(uint32_t)(kP0Seg - 1));
+      const uint32_t nfl = (rn != c0 && (plast || lim > c0)) ? rn - c0 : 0u;  // as at the read of cq below
+      if (nfl > 0) drec[c0] = cq0;
+      if (nfl > 1) drec[c0 + 1] = cq1;
+      if (nfl > 2) drec[c0 + 2] = cq2;
+      // one 16-byte store per record, or into the carry when its segment is not complete in this chunk yet
+#pragma unroll
+      for (int r = 0; r < kP0Items; ++r) {
+        const int s = r * kP0Block + tid;
+        if (s < ptile_n) {
+          const uint4 x = xb[s];
+          const uint32_t d = x.x & (kBins - 1);
+          const uint32_t rd = run[d], td = tstart[d];
+          const uint32_t dest = rd + (uint32_t)s - td;
+          const uint32_t ld = plast ? 0xffffffffu : ((rd + tstart[d + 1] - td) & ~(uint32_t)(kP0Seg - 1));
+          if (dest < ld) {
+            drec[dest] = x;
+          } else {
+            const uint32_t cd = cst[d];
+            carry[d][dest - (cd > ld ? cd : ld)] = x;
+          }
+        }
+      }
+      lds_barrier();  // every destination computed from run / cst before they advance; xb / tstart free again
+      run[tid] = rn + ct;
+      if (lim != 0xffffffffu && lim > c0) cst[tid] = lim;
+    }
+    if (!more) break;
 
     // stable rank within (wave, digit): wave64 ballot peer masks, in arrival order
-    uint32_t dg[kP0Items], lp[kP0Items];
+    uint32_t dg[kP0Items], lp = 0;  // lp: the four ranks, 8 bits each (< 256: a wave has 256 records of a tile)
+    static_assert(kP0Items * 64 <= 256 && kP0Items <= 4, "a record's rank within (wave, digit) fits 8 bits");
 #pragma unroll
     for (int k = 0; k < kP0Items; ++k) {
       const int e = w * 64 * kP0Items + k * 64 + lane;
@@ -129,18 +201,19 @@ __global__ void __launch_bounds__(kP0Block) pass0_kernel(Src src, uint4* __restr
       uint32_t old = 0;
       if (valid) old = wc[dg[k]][w];
       wave_lockstep();
-      const uint32_t below = (uint32_t)__popcll(peers & lt);
+      const uint32_t below = lanes_below(peers);
       if (valid && below == 0) wc[dg[k]][w] = (uint16_t)(old + (uint32_t)__popcll(peers));
       wave_lockstep();
-      lp[k] = old + below;
+      lp |= (old + below) << (8 * k);
     }
+    // the next tile's loads: no global store between here and their wait at the top of the next iteration
+    if (!last) load_tile(base + kP0Tile);
     lds_barrier();
 
     // digit tid: its tile count and the tile's digit starts (block scan)
-    uint32_t ct;
+    uint32_t ct = 0;
     {
       const uint4 r0 = row[0], r1 = row[1];
-      ct = 0;
       const uint32_t word[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
 #pragma unroll
       for (int i = 0; i < 8; ++i) ct = sm_udot2(word[i], 0x00010001u, ct);
@@ -157,39 +230,22 @@ __global__ void __launch_bounds__(kP0Block) pass0_kernel(Src src, uint4* __restr
     for (int k = 0; k < kP0Items; ++k) {
       const int e = w * 64 * kP0Items + k * 64 + lane;
       if (e < tile_n) {
-        const uint4* rr = (const uint4*)&wc[dg[k]][0];
-        xb[tstart[dg[k]] + p0_before(rr[0], rr[1], w) + lp[k]] = rec[k];
+        const uint32_t d = rec[k].x & (kBins - 1);  // (recomputed: dg[] is not kept across the scan)
+        const uint4* rr = (const uint4*)&wc[d][0];
+        xb[tstart[d] + p0_before(rr[0], rr[1], w) + ((lp >> (8 * k)) & 0xffu)] = rec[k];
       }
     }
-    if (!last) load_tile(base + kP0Tile);  // the next tile's loads overlap this tile's stores
-    // carried records of digit tid whose segment completes now (or the chunk ends) leave first
-    if (rn != c0 && (last || lim > c0))
-      for (uint32_t q = 0; q < rn - c0; ++q) drec[c0 + q] = carry[tid][q];
+    // carried records of digit tid whose segment completes now (or the chunk ends) leave first: read here, before
+    // the barrier that lets their slots be refilled, stored after the wait for the next tile's loads
+    const uint32_t nfl = (rn != c0 && (last || lim > c0)) ? rn - c0 : 0u;
+    if (nfl > 0) cq0 = carry[tid][0];
+    if (nfl > 1) cq1 = carry[tid][1];
+    if (nfl > 2) cq2 = carry[tid][2];
     lds_barrier();  // xb complete; the carry slots read above may be refilled; the count rows are read no more
     row[0] = make_uint4(0, 0, 0, 0);
     row[1] = make_uint4(0, 0, 0, 0);
-
-    // one 16-byte store per record, or into the carry when its segment is not complete in this chunk yet
-#pragma unroll
-    for (int r = 0; r < kP0Items; ++r) {
-      const int s = r * kP0Block + tid;
-      if (s < tile_n) {
-        const uint4 x = xb[s];
-        const uint32_t d = x.x & (kBins - 1);
-        const uint32_t rd = run[d], td = tstart[d];
-        const uint32_t dest = rd + (uint32_t)s - td;
-        const uint32_t ld = last ? 0xffffffffu : ((rd + tstart[d + 1] - td) & ~(uint32_t)(kP0Seg - 1));
-        if (dest < ld) {
-          drec[dest] = x;
-        } else {
-          const uint32_t cd = cst[d];
-          carry[d][dest - (cd > ld ? cd : ld)] = x;
-        }
-      }
-    }
-    lds_barrier();  // every destination computed from run / cst before they advance
-    run[tid] = rn + ct;
-    if (lim != 0xffffffffu && lim > c0) cst[tid] = lim;
+    ptile_n = tile_n;
+    plast = last;
   }
   src.flush();
 }

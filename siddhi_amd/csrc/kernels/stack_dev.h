@@ -285,6 +285,31 @@ __device__ SM_EXACT4_INLINE bool c2_exact4(const Stack4Cold* c, uint32_t cs, uin
                             c->o0, cs, ce, oi, oj);
 }
 
+// A per-lane value the optimiser cannot see through. What is computed from it is computed where it is used: without
+// it, thread-invariant values of the epoch loop (a zero uint4, LDS addresses) are hoisted out of the loop, do not fit
+// the 128 VGPRs and come back from scratch, and a scratch reload after the emission's stores waits for those stores.
+// No instruction.
+__device__ __forceinline__ uint32_t sm4_opaque(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(v));
+#endif
+  return v;
+}
+
+// The prefetched slice has arrived: the one wait of an epoch for vector memory. gfx9 counts vector loads and stores
+// in one in-order vmcnt, so the first use of pre[] after the emission's staging stores would also wait for those
+// stores; placed before them, it waits for loads issued an epoch ago and for nothing younger. No memory operation
+// moves across it. No instruction beyond the s_waitcnt the compiler puts in front of it.
+__device__ __forceinline__ void sm4_arrived(uint4 (&pre)[kI4]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+  for (int k = 0; k < kI4; ++k)
+    asm volatile("" : "+v"(pre[k].x), "+v"(pre[k].y), "+v"(pre[k].z), "+v"(pre[k].w) : : "memory");
+#else
+  (void)pre;
+#endif
+}
+
 #ifndef SM_RANK4_INLINE
 #define SM_RANK4_INLINE __forceinline__
 #endif
@@ -292,11 +317,13 @@ __device__ SM_EXACT4_INLINE bool c2_exact4(const Stack4Cold* c, uint32_t cs, uin
 // and arrival positions | c1, ordinals by arrival position
 __device__ SM_RANK4_INLINE void rank4(Slot4& S, const uint4 (&pre)[kI4], int sn, uint32_t* lw, bool fp,
                                        uint32_t* err) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63, w = wave_index();
   uint8_t* cnt = (uint8_t*)S.pk;  // [key][wave]
-  *(uint4*)(cnt + 16 * tid) = make_uint4(0, 0, 0, 0);
+  {
+    const uint32_t z = sm4_opaque(0u);  // (a zero made here, not one kept in four registers across the kernel)
+    *(uint4*)(cnt + 16 * tid) = make_uint4(z, z, z, z);
+  }
   lds_barrier();
-  const uint64_t lt = lanemask_lt();
   uint32_t hk[kI4], lp[kI4];
   bool nan = false;
 #pragma unroll
@@ -309,7 +336,7 @@ __device__ SM_RANK4_INLINE void rank4(Slot4& S, const uint4 (&pre)[kI4], int sn,
     uint32_t old = 0;
     if (valid) old = cnt[16 * hk[k] + w];
     wave_lockstep();
-    const uint32_t below = (uint32_t)__popcll(peers & lt);
+    const uint32_t below = lanes_below(peers);
     if (valid && below == 0) cnt[16 * hk[k] + w] = (uint8_t)(old + (uint32_t)__popcll(peers));
     wave_lockstep();
     lp[k] = old + below;
@@ -393,7 +420,7 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
     auto load = [&](uint32_t s) {
 #pragma unroll
       for (int k = 0; k < kI4; ++k) {
-        const uint32_t p = s * kSS + (tid >> 6) * 64 * kI4 + k * 64 + lane;
+        const uint32_t p = s * kSS + (uint32_t)wave_index() * 64 * kI4 + k * 64 + lane;
         if (p < blen) {
           typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
           const u32x4 v = __builtin_nontemporal_load((const u32x4*)recb + p);
@@ -533,6 +560,8 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
       SM4_PHASE(1);
       lds_barrier();  // every lane is done with slice e
       SM4_PHASE(2);
+      sm4_arrived(pre);  // slice e + kR, loaded during the epoch before (unconditional: a wait under a condition
+                         // leaves the compiler its own wait at rank4's first use, behind the stores)
 
       // ---- slice e's matches, in arrival order of j
       {
@@ -566,7 +595,7 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
         if (tid == 0) s_tot = tot;
         lds_barrier();
         const uint32_t np = s_pool[q0] < (uint32_t)kPool ? s_pool[q0] : (uint32_t)kPool;
-        for (uint32_t k = tid; k < np; k += kT4) {
+        for (uint32_t k = sm4_opaque((uint32_t)tid); k < np; k += kT4) {
           const uint2 pe = S.pool[k];
           const uint32_t p = pe.y & 0xffffu, kk = pe.y >> 16;
 #ifdef SM_EMU_DEBUG
