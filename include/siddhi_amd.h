@@ -125,7 +125,10 @@ int sm_input_send(sm_input* in, int64_t timestamp, const sm_value* row, size_t n
  * `every e1 -> e2 within T` patterns: it is processed inside the call, on the device-batch pipelines (closed form,
  * carried partials shared with device batches), uploaded in chunks of option "bulk_chunk" events (default 2^24) with
  * the upload of the next chunk overlapping the processing of the current one, and its outputs reach the callbacks
- * chunk by chunk before the call returns. Staged events of such an app take the same pipelines at flush. */
+ * chunk by chunk before the call returns. Staged events of such an app take the same pipelines at flush. Such a batch
+ * also goes to the device directly when some queries are `every e1=S[c1], e2=S[c2] [within T]` sequences (the
+ * adjacent-pair closed form, sm_app_process_device_batch); staged events of an app with such a sequence run on the
+ * general NFA kernel, which then keeps the sequence's matching state ("nfa_state:<query>" = 1, "fast_path" 5). */
 int sm_input_send_columns(sm_input* in, size_t n, const int64_t* timestamps, const void* const* cols,
                           const uint8_t* const* null_flags);
 
@@ -172,10 +175,14 @@ size_t sm_app_dump_outputs(sm_app* app, char* buf, size_t len);
 int sm_app_set_option(sm_app* app, const char* key, int64_t value);
 
 /* Device-resident batch of ONE stream (columns already in HBM, hipStream given as void*): the device form of a
- * sequence of InputHandler.send(ts, row) calls on that stream. Filter queries and `every e1 -> e2 within T` patterns
- * run on the GPU; the pattern is a streaming receiver: each key's open partials are carried into the next batch
+ * sequence of InputHandler.send(ts, row) calls on that stream. Filter queries, `every e1 -> e2 within T` patterns and
+ * `every e1=S[c1], e2=S[c2] [within T]` sequences (both elements on this stream, no having) run on the GPU; the
+ * pattern is a streaming receiver: each key's open partials are carried into the next batch
  * (StreamPreStateProcessor's pending list across sends), and a batch that leaves the closed form's premise (event
- * time going back, a condition outside its envelope) hands the query to the general NFA kernel for good. The match
+ * time going back, a condition outside its envelope) hands the query to the general NFA kernel for good. The
+ * sequence is the set of adjacent pairs of each partition instance (a partial is completed or dropped by the
+ * instance's next event): it carries at most one event per key, and event time may go back unless it has a `within`;
+ * partition keys are a single INT / LONG attribute, other key forms take the NFA kernel. The match
  * tuples stay on the device (sm_app_device_matches); when a StreamCallback / QueryCallback is registered for a query
  * (or the collect dump is on), its outputs are also projected on the device and delivered as Events before the
  * call returns, in reference order, one callback call per input event that produced output
@@ -297,9 +304,10 @@ int sm_app_device_project(sm_app* app, const char* query_name, sm_dval* d_values
                           size_t* n, int32_t* nsel, void* hip_stream);
 /* Diagnostics of the last device batch: "fast_path:<query>" = the device path it took: patterns 3 = bucket-stack
  * kernels, 2 = sort / walk kernels, 1 = general closed form (option fast_general), 5 = general NFA kernel (hand-over);
- * filter queries 3 = filter interpreter, 4 = typed conjunction. "output_events:<query>" = its output count.
+ * `every e1, e2` sequences 6 = adjacent-pair kernels (labels seq_facts, seq_sort, seq_link, seq_keep, seq_count,
+ * seq_scan, seq_emit, seq_carry), 5 = general NFA kernel; filter queries 3 = filter interpreter, 4 = typed conjunction. "output_events:<query>" = its output count.
  * "kernel_ms:<label>" / "kernel_calls:<label>" and "fast_ms:group" / "fast_ms:walk" / "fast_ms:order" (per-kernel
- * and phase times in ms; need the "fast_timing" option). "nfa_state:<query>" = 1 once a closed-form pattern's matching
+ * and phase times in ms; need the "fast_timing" option). "nfa_state:<query>" = 1 once a closed-form query's matching
  * state is held by the general NFA kernel for good: host events it could not take on the closed form (a null value,
  * a chained or broadcast app) or a device batch outside its premise (event time decreasing) handed its carried
  * partials over, and every later batch of that query runs on the NFA kernel (same results, the NFA's speed).

@@ -729,9 +729,11 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
     code = std::move(lw.code);
     consts = std::move(lw.consts);
 
-    // ---- fast path detection: every e1=S[c1] -> e2=S[c2] (within T on e2), pattern, 2 slots
+    // ---- fast path detection: every e1=S[c1] -> e2=S[c2] (within T on e2), pattern, 2 slots; and its sequence
+    // sibling every e1=S[c1], e2=S[c2]
     const StateElem* root_el = q.state.get();
-    if (q.input == InputKind::PATTERN && root_el->kind == StateKind::NEXT && !root_el->has_within &&
+    if ((q.input == InputKind::PATTERN || q.input == InputKind::SEQUENCE) && root_el->kind == StateKind::NEXT &&
+        !root_el->has_within &&
         root_el->a->kind == StateKind::EVERY && root_el->a->a->kind == StateKind::STREAM && !root_el->a->has_within &&
         !root_el->a->a->has_within && root_el->b->kind == StateKind::STREAM &&
         root_el->a->a->stream_id == root_el->b->stream_id && h.nslots == 2) {
@@ -740,7 +742,9 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
       for (size_t k = 0; k < refs.size(); k += 2)
         if (!(refs[k + 1] == 0 || refs[k + 1] == kCurrent)) ok = false;
       if (ok) {
-        cq.fast_every_within = true;
+        // a sequence of the same shape: every partial lives for one event of its instance (kernels/seq_dev.h)
+        if (q.input == InputKind::SEQUENCE) cq.fast_seq_adjacent = true;
+        else cq.fast_every_within = true;
         cq.fast_within = root_el->b->has_within ? root_el->b->within_ms : -1;
         cq.fast_c1_off = pres[0].progOff;
         cq.fast_c1_len = pres[0].progLen;
@@ -756,7 +760,7 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
   h.nwithin = (int)withins.size();
   h.nsel = (int)cq.sel_types.size();
   h.nrefs_vis = (int)refs.size() / 2;
-  if (cq.fast_every_within) {  // hidden (e1, e2) ordinals for the NFA fallback of device batches
+  if (cq.fast_every_within || cq.fast_seq_adjacent) {  // hidden (e1, e2) ordinals for the NFA fallback of device batches
     refs.insert(refs.end(), {0, 0, 1, 0});
   }
   h.nrefs = (int)refs.size() / 2;

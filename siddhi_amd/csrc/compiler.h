@@ -40,6 +40,9 @@ struct CompiledQuery {
   int64_t fast_within = -1;             // -1 = no within
   int fast_c1_off = 0, fast_c1_len = 0; // program over e1's stream columns (stream context)
   int fast_c2_off = 0, fast_c2_len = 0; // program over (e1 slot 0, e2 slot 1) state context
+  // fast path: every e1=S[c1], e2=S[c2] [within T] (sequence: adjacent pairs of a partition instance, seqpath.hip);
+  // shares fast_within / fast_c1_* / fast_c2_*
+  bool fast_seq_adjacent = false;
 };
 
 struct CompiledPartition {

@@ -42,7 +42,7 @@ struct FastState {
   int cus = 0;              // compute units of the device
   int sort_wgs_per_cu = 0;  // resident down-sweep workgroups per CU (persistent-chunk grid)
   int walk_wgs_per_cu = 0;  // resident walk workgroups per CU
-  int last_path = 0;        // pipeline of the last batch: 2 = sort / walk, 3 = bucket stack
+  int last_path = 0;        // pipeline of the last batch: 2 = sort / walk, 3 = bucket stack, 6 = adjacent pairs
 };
 
 struct FastTimings {          // optional HIP events: [0] start, [1] keyed sort done, [2] walk done, [3] end
@@ -97,6 +97,15 @@ enum : int64_t { FAST_OUTSIDE = -1, FAST_NON_MONOTONE = -2, FAST_KEY_SPAN = -3 }
 int64_t fast_every_within_v2(const FastArgs& a, const FastHostInfo& hi, FastState& fs, FastCarry& carry,
                              uint32_t* pairs_out, int64_t pairs_cap, Scratch& sc, hipStream_t s,
                              FastTimings* tm = nullptr, int stack_mode = 0);
+
+// The adjacent-pair closed form of `every e1=S[c1], e2=S[c2] [within T]` (seqpath.hip, seq_dev.h): a sequence's
+// partial is completed or dropped by the next event of its partition instance, so the outputs are adjacent pairs, at
+// most one per e2, in order of e2. Same results, pairs and carry conventions as fast_every_within_v2 (the carry holds at
+// most one row per key: the key's last event if it passes c1; hi.vattr is not used: c1 and c2 are evaluated by the
+// bytecode interpreter on the columns). FAST_NON_MONOTONE is returned only when a.within >= 0; FAST_KEY_SPAN only for a
+// query's first batch with hi.remap_span set. Sets fs.last_path = 6.
+int64_t fast_seq_adjacent(const FastArgs& a, const FastHostInfo& hi, FastState& fs, FastCarry& carry,
+                          uint32_t* pairs_out, int64_t pairs_cap, Scratch& sc, hipStream_t s, FastTimings* tm = nullptr);
 
 // ---- internal: the bucket-stack pipeline (stack.hip), entered by fast_every_within_v2 after key pass 0 ----
 

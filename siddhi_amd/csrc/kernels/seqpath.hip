@@ -1,0 +1,276 @@
+// Host entry of the adjacent-pair closed form of `every e1=S[c1], e2=S[c2] [within T]` (seq_dev.h has the rule and
+// the kernels). Per batch:
+//   facts   one streaming pass over the key column, event times and ordinals: key range, decreasing event time,
+//           ordinals that do not fit (the only host round trip before the carry is touched)
+//   keyed   stable LSD sort of (key - kmin, row) (primitives.hip), so each event's predecessor is its left neighbour
+//   link    seq_link_kernel: e1 (or none) at every e2's row, carry-out candidates, carried rows that saw an event
+//   emit    tile counts (from the link pass in row order, seq_count_kernel after a key sort), their scan, then the
+//           pairs in row order; each e2 has at most one pair, so this is the reference's order and nothing is sorted
+//   carry   one row per key whose last event passes c1 (build_carry); keys without events keep their row
+#include "fastpath.h"
+#include "seq_dev.h"
+
+namespace sm {
+
+namespace {
+
+struct SeqFacts {
+  unsigned long long kmin, kmax;  // sign-biased key range
+  unsigned int bad_ts, bad_ord, bad_carry, pad;
+  long long o0, omax;             // relative ordinals of the first and the last event
+  long long ts0, ts_last;
+};
+
+constexpr int kFactsBlock = 256;
+
+template <typename KT>
+__global__ void __launch_bounds__(kFactsBlock) seq_facts_kernel(const KT* __restrict__ kcol,
+                                                                const int64_t* __restrict__ ts,
+                                                                const int64_t* __restrict__ ord, int64_t obase,
+                                                                int64_t n, SeqFacts* __restrict__ f) {
+  uint64_t lo = ~0ull, hi = 0;
+  bool bts = false, bord = false;
+  for (int64_t i = (int64_t)blockIdx.x * kFactsBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kFactsBlock) {
+    if (kcol) {
+      const uint64_t u = (uint64_t)(int64_t)kcol[i] ^ 0x8000000000000000ull;
+      lo = u < lo ? u : lo;
+      hi = u > hi ? u : hi;
+    }
+    const int64_t t = ts[i];
+    if (i > 0) bts |= t < ts[i - 1];
+    if (ord && i > 0) bord |= ord[i] <= ord[i - 1];
+    if (i == 0) {
+      f->ts0 = t;
+      f->o0 = ord ? ord[0] - obase : 0;
+    }
+    if (i == n - 1) {
+      f->ts_last = t;
+      f->omax = ord ? ord[i] - obase : i;
+    }
+  }
+  if (kcol) {
+    for (int o = 32; o > 0; o >>= 1) {
+      const uint64_t x = __shfl_down(lo, o, 64), y = __shfl_down(hi, o, 64);
+      lo = x < lo ? x : lo;
+      hi = y > hi ? y : hi;
+    }
+    if ((threadIdx.x & 63) == 0 && hi >= lo) {
+      atomicMin(&f->kmin, (unsigned long long)lo);
+      atomicMax(&f->kmax, (unsigned long long)hi);
+    }
+  }
+  const bool any_ts = __any(bts), any_ord = __any(bord);
+  if ((threadIdx.x & 63) == 0) {
+    if (any_ts) atomicOr(&f->bad_ts, 1u);
+    if (any_ord) atomicOr(&f->bad_ord, 1u);
+  }
+}
+
+// carried e1 ordinals must lie in (base - 2^31, base): pair_project tells them from batch rows by their sign
+__global__ void seq_carry_check_kernel(const int64_t* __restrict__ rows, int64_t nc, int cw, int64_t obase,
+                                       SeqFacts* __restrict__ f) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  const int64_t o = rows[c * cw + 1] - obase;
+  if (o >= 0 || o <= (int64_t)INT32_MIN) atomicOr(&f->bad_carry, 1u);
+}
+
+template <typename KT, typename K>
+__global__ void seq_sort_keys_kernel(const KT* __restrict__ kcol, int64_t n, int64_t kmin, K* __restrict__ sk,
+                                     uint32_t* __restrict__ idx) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  sk[i] = (K)((uint64_t)(int64_t)kcol[i] - (uint64_t)kmin);
+  idx[i] = (uint32_t)i;
+}
+
+inline dim3 seq_grid(int64_t n, int t) { return dim3((unsigned)std::max<int64_t>(1, (n + t - 1) / t)); }
+
+int bits_of(uint64_t x) {
+  int b = 0;
+  while (b < 64 && (x >> b) != 0) ++b;
+  return b;
+}
+
+}  // namespace
+
+int64_t fast_seq_adjacent(const FastArgs& a, const FastHostInfo& hi, FastState& fs, FastCarry& carry,
+                          uint32_t* pairs_out, int64_t pairs_cap, Scratch& sc, hipStream_t s, FastTimings* tm) {
+  const int64_t n = a.n;
+  if (n == 0) return 0;
+  if (n >= 0x7fffffffll) return FAST_OUTSIDE;
+  const bool keyed = a.key != nullptr;
+  if (keyed && (hi.key_col < 0 || !(hi.key_type == T_INT || hi.key_type == T_LONG))) return FAST_OUTSIDE;
+  const size_t mark = sc.used;
+  if (tm) {
+    SM_HIP(hipEventRecord(tm->ev[0], s));
+    tm->nmk = 0;
+    tm->mark("start", s);
+  }
+  auto tmark = [&](const char* l) {
+    if (tm) tm->mark(l, s);
+  };
+  const void* kcol = keyed ? (hi.dense_keys ? (const void*)hi.dense_keys : hi.cols[hi.key_col]) : nullptr;
+  const bool key64 = keyed && !hi.dense_keys && hi.key_type == T_LONG;
+  const int nattr = hi.nattr, cw = 3 + nattr;
+  const int64_t nc = carry.n;
+
+  // ---- facts: nothing is changed before they are read
+  SeqFacts* f = (SeqFacts*)sc.take(sizeof(SeqFacts));
+  {
+    SeqFacts init{};
+    init.kmin = ~0ull;
+    SM_HIP(hipMemcpyAsync(f, &init, sizeof(SeqFacts), hipMemcpyHostToDevice, s));
+  }
+  const dim3 fgrid((unsigned)std::min<int64_t>(2048, (n + kFactsBlock - 1) / kFactsBlock));
+  if (key64)
+    hipLaunchKernelGGL(seq_facts_kernel<int64_t>, fgrid, dim3(kFactsBlock), 0, s, (const int64_t*)kcol, a.ts, a.ordinals,
+                       a.ordinal_base, n, f);
+  else
+    hipLaunchKernelGGL(seq_facts_kernel<int32_t>, fgrid, dim3(kFactsBlock), 0, s, (const int32_t*)kcol, a.ts, a.ordinals,
+                       a.ordinal_base, n, f);
+  if (nc > 0)
+    hipLaunchKernelGGL(seq_carry_check_kernel, seq_grid(nc, 256), dim3(256), 0, s, (const int64_t*)carry.rows, nc,
+                       carry.width, a.ordinal_base, f);
+  tmark("seq_facts");
+  SeqFacts h;
+  SM_HIP(hipMemcpyAsync(&h, f, sizeof(SeqFacts), hipMemcpyDeviceToHost, s));
+  SM_HIP(hipStreamSynchronize(s));
+  auto leave = [&](int64_t r) {
+    sc.used = mark;
+    return r;
+  };
+  // with a within, a partial older than T is dropped only because event time never goes back
+  if (a.within >= 0 && (h.bad_ts || (carry.active && h.ts0 < carry.ts_last))) return leave(FAST_NON_MONOTONE);
+  if (h.bad_ord || h.bad_carry || h.o0 < 0 || h.omax >= 0x7fffffffll) return leave(FAST_OUTSIDE);
+  if (nc > 0 && carry.width != cw) return leave(FAST_OUTSIDE);
+  int64_t kmin = 0;
+  int kbits = 0;
+  if (keyed) {
+    kmin = (int64_t)(h.kmin ^ 0x8000000000000000ull);
+    const uint64_t kspan = (uint64_t)((int64_t)(h.kmax ^ 0x8000000000000000ull) - kmin);
+    kbits = std::max(1, bits_of(kspan));
+    // a query's first batch decides between key values and dense ids when the caller offers them (remap_span: it
+    // gives the ids and runs the batch again); once rows are carried their keys stay what they are: any span is sorted
+    if (!carry.active && hi.remap_span > 0 && (kbits > 30 || kspan > (uint64_t)hi.remap_span))
+      return leave(FAST_KEY_SPAN);
+  }
+
+  // what the carry-out reads lies first, so that the rest is free again when build_carry runs
+  const int64_t cand_cap = n + nc;
+  {  // scratch for the worst case, before anything changes: sort pairs + links, then the carry build per candidate
+    const uint64_t kmax_runs = keyed ? (kbits >= 62 ? (uint64_t)n : std::min<uint64_t>((uint64_t)n, (1ull << kbits))) : 1;
+    // sort pairs twice over (+ a histogram word per 4 events), links, tile counts
+    const size_t link = (size_t)n * (keyed ? (kbits > 32 ? 29 : 21) : 4) + (size_t)(n / kSeqTile + 2) * 4 + (8 << 20);
+    const size_t build = (size_t)(kmax_runs + (uint64_t)nc) * (size_t)(8 * cw + 44) + (8 << 20);
+    if (sc.used + (size_t)cand_cap * 32 + (size_t)nc + std::max(link, build) + 4096 > sc.cap) return leave(FAST_OUTSIDE);
+  }
+  uint32_t* ctl = (uint32_t*)sc.take(8);  // [0] candidates, [1] pairs
+  uint8_t* used = (uint8_t*)sc.take((size_t)std::max<int64_t>(nc, 1));
+  int64_t* cand = (int64_t*)sc.take((size_t)cand_cap * 32);
+  const size_t keep = sc.used;
+
+  // ---- keyed: rows in (key, arrival) order
+  const uint32_t* perm = nullptr;
+  const void* skey = nullptr;
+  const bool wide = kbits > 32;
+  if (keyed) {
+    uint32_t* si = (uint32_t*)sc.take((size_t)n * 4);
+    uint32_t* si2 = (uint32_t*)sc.take((size_t)n * 4);
+    const dim3 g = seq_grid(n, 256);
+    if (wide) {
+      uint64_t* sk = (uint64_t*)sc.take((size_t)n * 8);
+      uint64_t* sk2 = (uint64_t*)sc.take((size_t)n * 8);
+      hipLaunchKernelGGL((seq_sort_keys_kernel<int64_t, uint64_t>), g, dim3(256), 0, s, (const int64_t*)kcol, n, kmin,
+                         sk, si);
+      const bool alt = radix_sort_pairs<uint64_t>(sk, sk2, si, si2, (size_t)n, 0, kbits, sc, s);
+      skey = alt ? sk2 : sk;
+      perm = alt ? si2 : si;
+    } else {
+      uint32_t* sk = (uint32_t*)sc.take((size_t)n * 4);
+      uint32_t* sk2 = (uint32_t*)sc.take((size_t)n * 4);
+      if (key64)
+        hipLaunchKernelGGL((seq_sort_keys_kernel<int64_t, uint32_t>), g, dim3(256), 0, s, (const int64_t*)kcol, n, kmin,
+                           sk, si);
+      else
+        hipLaunchKernelGGL((seq_sort_keys_kernel<int32_t, uint32_t>), g, dim3(256), 0, s, (const int32_t*)kcol, n, kmin,
+                           sk, si);
+      const bool alt = radix_sort_pairs<uint32_t>(sk, sk2, si, si2, (size_t)n, 0, kbits, sc, s);
+      skey = alt ? sk2 : sk;
+      perm = alt ? si2 : si;
+    }
+    tmark("seq_sort");
+  }
+  if (tm) SM_HIP(hipEventRecord(tm->ev[1], s));
+
+  // ---- link
+  const int64_t ntiles = (n + kSeqTile - 1) / kSeqTile;
+  SM_HIP(hipMemsetAsync(ctl, 0, 8, s));
+  if (nc > 0) SM_HIP(hipMemsetAsync(used, 0, (size_t)nc, s));
+  SeqArgs sa{};
+  sa.n = n;
+  sa.ts = a.ts;
+  sa.st = a.st;
+  sa.code = a.code;
+  sa.consts = a.consts;
+  sa.c1_off = a.c1_off;
+  sa.c1_len = a.c1_len;
+  sa.c2_off = a.c2_off;
+  sa.c2_len = a.c2_len;
+  sa.within = a.within;
+  sa.ordinals = a.ordinals;
+  sa.obase = a.ordinal_base;
+  sa.perm = perm;
+  sa.skey = skey;
+  sa.kmin = kmin;
+  sa.carry = (const int64_t*)carry.rows;
+  sa.nc = nc;
+  sa.cw = cw;
+  sa.e1 = (int32_t*)sc.take((size_t)n * 4);
+  sa.used = used;
+  sa.cand = cand;
+  sa.cand_n = ctl;
+  uint32_t* counts = (uint32_t*)sc.take((size_t)(ntiles + 1) * 4);
+  sa.counts = keyed ? nullptr : counts;
+  if (wide) hipLaunchKernelGGL(seq_link_kernel<uint64_t>, dim3((unsigned)ntiles), dim3(kSeqBlock), 0, s, sa);
+  else hipLaunchKernelGGL(seq_link_kernel<uint32_t>, dim3((unsigned)ntiles), dim3(kSeqBlock), 0, s, sa);
+  tmark("seq_link");
+  if (nc > 0) {
+    hipLaunchKernelGGL(seq_keep_kernel, seq_grid(nc, kSeqBlock), dim3(kSeqBlock), 0, s, (const int64_t*)carry.rows, nc, cw,
+                       (const uint8_t*)used, sa.cand, ctl);
+    tmark("seq_keep");
+  }
+  if (tm) SM_HIP(hipEventRecord(tm->ev[2], s));
+
+  // ---- pairs in row order
+  if (keyed) {
+    hipLaunchKernelGGL(seq_count_kernel, dim3((unsigned)ntiles), dim3(kSeqBlock), 0, s, (const int32_t*)sa.e1, n, counts);
+    tmark("seq_count");
+  }
+  exclusive_scan_u32(counts, (size_t)ntiles, sc, s, ctl + 1);
+  tmark("seq_scan");
+  hipLaunchKernelGGL(seq_emit_kernel, dim3((unsigned)ntiles), dim3(kSeqBlock), 0, s, (const int32_t*)sa.e1, n,
+                     (const uint32_t*)counts, a.ordinals, a.ordinal_base, pairs_out);
+  tmark("seq_emit");
+  uint32_t hc[2] = {0, 0};
+  SM_HIP(hipMemcpyAsync(hc, ctl, 8, hipMemcpyDeviceToHost, s));
+  SM_HIP(hipStreamSynchronize(s));
+  const int64_t m = hc[1];
+  if (m > pairs_cap || (int64_t)hc[0] > cand_cap) {  // cannot happen (m <= n <= pairs_cap): checked, not assumed
+    sc.used = mark;
+    throw std::runtime_error("adjacent-pair closed form: output larger than its buffer");
+  }
+
+  // ---- carry out (build_carry reads the old rows before it replaces them)
+  sc.used = keep;
+  build_carry(sa.cand, (int64_t)hc[0], a.st, nattr, carry, sc, s, 64, 0, true);
+  tmark("seq_carry");
+  carry.ts_last = carry.active ? std::max<int64_t>(carry.ts_last, h.ts_last) : (int64_t)h.ts_last;
+  carry.active = true;
+  fs.last_path = 6;
+  if (tm) SM_HIP(hipEventRecord(tm->ev[3], s));
+  sc.used = mark;
+  return m;
+}
+
+}  // namespace sm

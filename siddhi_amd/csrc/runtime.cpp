@@ -365,8 +365,8 @@ struct QueryRt {
   bool nfa_mode = false;     // a closed-form query handed to the NFA kernel for good (nfa_device_batch)
   int level = 0;             // chaining depth: 0 reads input streams only, L reads a stream a level L-1 query fills
   int nfa_kernel_used = 0;   // 1 = query-specialised NFA kernel, 2 = interpreter (last batch this query ran on the NFA)
-  int fast_path_used = 0;    // 5 = NFA kernel, 3 = bucket stack, 2 = onesweep form, 1 = general form (last device
-                             // batch)
+  int fast_path_used = 0;    // 6 = adjacent pairs (sequence), 5 = NFA kernel, 3 = bucket stack, 2 = onesweep form,
+                             // 1 = general form (last device batch)
   // what sm_app_device_project needs of the last closed-form batch: its stream, event times, ordinals, and the
   // carry as it was before the batch (carried e1 rows)
   bool proj_ok = false;
@@ -422,6 +422,26 @@ int fast_vattr(const CompiledQuery& cq, const std::vector<int32_t>& types) {
   if (vattr >= (int)types.size() || types[vattr] == T_STRING || types[vattr] == T_BOOL) return -1;
   return vattr;
 }
+
+// The adjacent-pair kernels (seqpath.hip) evaluate c1 on one row and c2 on (e1, e2) single events: no timestamp
+// reads, slots 0 / 1 at index 0 or CURRENT only.
+bool seq_progs_ok(const CompiledQuery& cq) {
+  const Instr* code = (const Instr*)(cq.blob.data() + cq.hdr.off_code);
+  for (int k = 0; k < cq.fast_c2_len; ++k) {
+    const Instr& in = code[cq.fast_c2_off + k];
+    if (in.op == OP_TS || in.op == OP_COL) return false;
+    if (in.op == OP_VAR && (in.a < 0 || in.a > 1 || !(in.b == 0 || in.b == -1))) return false;
+  }
+  for (int k = 0; k < cq.fast_c1_len; ++k) {
+    const Instr& in = code[cq.fast_c1_off + k];
+    if (in.op == OP_TS) return false;
+    if (in.op == OP_VAR && (in.a != 0 || !(in.b == 0 || in.b == -1))) return false;
+  }
+  return true;
+}
+
+// A query with a closed form over device batches: the pattern `every e1 -> e2 within T` or its sequence sibling.
+inline bool closed_form(const CompiledQuery& cq) { return cq.fast_every_within || cq.fast_seq_adjacent; }
 
 }  // namespace
 }  // namespace sm
@@ -1504,7 +1524,10 @@ size_t batch_scratch(const sm_app* a, int64_t N) {
 // arrival order: each replayed event passes c1 again and re-creates its partial, and as an e2 candidate it meets
 // only replayed partials of its own key that it already failed when it first arrived (a partial is still open
 // only because every later event of its key failed c2 without expiring it: isExpired :102-121), so the replay
-// emits nothing. The batch's matches go to dev_pairs as in the closed form: (e1, e2) relative to ordinal_base,
+// emits nothing. The same holds for the carries of the sequence `every e1, e2` (seqpath.hip): at most one carried
+// e1 per partition instance, the instance's last event, so a replayed event meets no partial at all and the replay
+// emits nothing; it passes c1 again and is the pending e1 of its instance when the batch's first event arrives, as in
+// the reference. The batch's matches go to dev_pairs as in the closed form: (e1, e2) relative to ordinal_base,
 // in reference order.
 int64_t nfa_device_batch(sm_app* a, int qi, int s, size_t n, const int64_t* d_ts, const void* const* d_cols,
                          const int64_t* d_ordinals, int64_t ordinal_base, hipStream_t hs, std::vector<HostOut>* douts) {
@@ -2413,8 +2436,9 @@ void run_chained(sm_app* a, std::vector<HostOut>& outs) {
 }
 
 // The device-batch path of one stream (sm_app_process_device_batch, and host-API batches of apps whose queries all
-// take it: flush_device): every query reading stream s runs over the n events (columns, event times and ordinals
-// in device memory) on hs; the outputs that have consumers are appended to douts (host copies in out_arena).
+// take it: flush_device; large columnar sends: bulk_send_device): every query reading stream s runs over the n
+// events (columns, event times and ordinals in device memory) on hs; the outputs that have consumers are appended to
+// douts (host copies in out_arena).
 void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const void* const* d_cols,
                          const int64_t* d_ordinals, int64_t ordinal_base, hipStream_t hs, std::vector<HostOut>& douts,
                          std::vector<DevOut>& draw) {
@@ -2423,10 +2447,11 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
   for (auto& bc : a->part_bcast)
     if (!bc.empty()) throw sql::UnsupportedError("partitions reading unkeyed streams run through the host API");
   for (auto& qp : a->queries)
-    if (qp->cq.hdr.kind != 0 && !qp->cq.fast_every_within &&
+    if (qp->cq.hdr.kind != 0 && !closed_form(qp->cq) &&
         std::find(qp->cq.streams.begin(), qp->cq.streams.end(), s) != qp->cq.streams.end())
-      throw sql::UnsupportedError("device batches support filter queries and `every e1 -> e2 within T` patterns; "
-                                  "query '" + qp->cq.name + "' takes sm_app_process_device_events or the host API");
+      throw sql::UnsupportedError("device batches support filter queries, `every e1 -> e2 within T` patterns and "
+                                  "`every e1, e2 [within T]` sequences; query '" + qp->cq.name +
+                                  "' takes sm_app_process_device_events or the host API");
   StreamStage& st = a->streams[s];
   NfaStream d;
   memset(&d, 0, sizeof(d));
@@ -2447,6 +2472,12 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
     need = std::max(need, cq.hdr.kind == 0 ? n / 8 + n / 1024 + (64 << 20)
                                            : n * 68 + std::min<size_t>(n + nc, (size_t)1 << 26) * 32 +
                                                  nc * (160 + 8 * wc) + ((size_t)640 << 20));
+    // sequences (seqpath.hip): sort pairs, links, dense ids (40 B per event), candidates (32 B per event and carried
+    // row) and the carry build's rows and sort arrays for up to 2^24 keys with events plus the carried ones (a batch
+    // with more distinct keys than fit is refused by the kernels' host entry before anything changes)
+    if (cq.fast_seq_adjacent)
+      need = std::max(need, n * 40 + (n + nc) * 32 + (std::min<size_t>(n, (size_t)1 << 24) + nc) * (48 + 8 * wc) +
+                                ((size_t)64 << 20));
   }
   ensure_scratch(a, need);
   for (size_t qi = 0; qi < a->queries.size(); ++qi) {
@@ -2508,7 +2539,7 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
     FastHostInfo hi;
     hi.cols = d_cols;
     hi.types = types.data();
-    hi.vattr = fast_vattr(cq, types);
+    hi.vattr = cq.fast_seq_adjacent ? -1 : fast_vattr(cq, types);
     hi.c2_host = (const Instr*)(cq.blob.data() + cq.hdr.off_code) + cq.fast_c2_off;
     hi.c2_len = cq.fast_c2_len;
     hi.c1_host = (const Instr*)(cq.blob.data() + cq.hdr.off_code) + cq.fast_c1_off;
@@ -2527,7 +2558,7 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
     // partition keys as dense ids (any key domain): decided at the query's first closed-form batch, then kept, since
     // the carried partials hold ids; ValuePartitionExecutor (core/partition/executor/ValuePartitionExecutor.java:34-39)
     // keys by any value, so a sparse 64-bit id must not leave the closed form
-    if (fa.key && hi.key_col >= 0 && !a->force_general_fast && n > 0) {
+    if (fa.key && hi.key_col >= 0 && (!a->force_general_fast || cq.fast_seq_adjacent) && n > 0) {
       if (q.remap == 0 && !q.carry.active) {
         // option "key_remap", or (automatic) ids when the first batch's key span exceeds the bucket-stack window
         // (2^20): the batch runs on the values with remap_span set, and its prep pass reports a wider span
@@ -2548,10 +2579,19 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
       q.prev_carry.ensure(cb);
       SM_HIP(hipMemcpyAsync(q.prev_carry.p, q.carry.rows, cb, hipMemcpyDeviceToDevice, hs));
     }
+    // the closed form of this query: the pattern's pipelines, or the sequence's adjacent-pair kernels (path 6)
+    const bool seq = cq.fast_seq_adjacent;
+    auto closed = [&]() -> int64_t {
+      if (seq)
+        return seq_progs_ok(cq) ? fast_seq_adjacent(fa, hi, q.fast, q.carry, (uint32_t*)q.dev_pairs.p,
+                                                    (int64_t)(n + q.carry.n), a->sc, hs,
+                                                    a->fast_timing ? &a->fast_tm : nullptr)
+                                : (int64_t)FAST_OUTSIDE;
+      return fast_every_within_v2(fa, hi, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, (int64_t)(n + q.carry.n), a->sc,
+                                  hs, a->fast_timing ? &a->fast_tm : nullptr, a->fast_stack);
+    };
     int64_t m = FAST_OUTSIDE;
-    if (!a->force_general_fast)
-      m = fast_every_within_v2(fa, hi, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, (int64_t)(n + q.carry.n), a->sc, hs,
-                               a->fast_timing ? &a->fast_tm : nullptr, a->fast_stack);
+    if (!a->force_general_fast || seq) m = closed();
     if (m == FAST_KEY_SPAN && q.remap != 1 && a->key_remap < 0 && fa.key && hi.key_col >= 0) {
       // the first batch's keys span more than the bucket-stack window, or a later batch's keys leave the span the
       // first batch showed: dense ids from here on, for the carried partials' keys too (each key's rows stay one
@@ -2565,12 +2605,11 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
       int32_t* dk = (int32_t*)a->sc.take(n * 4);
       remap_keys(q.dense, hi.cols[hi.key_col], hi.key_type, (int64_t)n, dk, hs);
       hi.dense_keys = dk;
-      m = fast_every_within_v2(fa, hi, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, (int64_t)(n + q.carry.n), a->sc, hs,
-                               a->fast_timing ? &a->fast_tm : nullptr, a->fast_stack);
+      m = closed();
     }
     if (q.remap == 0 && hi.remap_span > 0 && m != FAST_OUTSIDE) q.remap = 2;  // the span fitted: values from here on
     q.fast_path_used = q.fast.last_path;
-    if (m == FAST_OUTSIDE && a->force_general_fast && q.carry.n == 0) {
+    if (m == FAST_OUTSIDE && a->force_general_fast && q.carry.n == 0 && !seq) {
       // diagnostic (option "fast_general"): the stateless general closed form, one batch at a time
       m = fast_every_within(fa, (uint32_t*)q.dev_pairs.p, (int64_t)n, a->sc, hs, a->fast_timing ? &a->fast_tm : nullptr);
       q.fast_path_used = 1;
@@ -2625,6 +2664,19 @@ bool app_device_ok(const sm_app* a) {
   return true;
 }
 
+// Whether a large columnar send (bulk_send_device) goes straight to the device-batch path: as app_device_ok, with the
+// `every e1, e2` sequences of the adjacent-pair closed form admitted too. Their staged host events keep running on the
+// NFA kernel (app_device_ok is unchanged, so flush() takes run_level for such an app); a bulk send after staged ones
+// then finds nfa_used set and its device batches run on the NFA as well (path 5), with one matching state.
+bool app_bulk_device_ok(const sm_app* a) {
+  if (a->max_level > 0) return false;
+  for (auto& bc : a->part_bcast)
+    if (!bc.empty()) return false;
+  for (auto& q : a->queries)
+    if (q->cq.hdr.kind != 0 && !closed_form(q->cq)) return false;
+  return true;
+}
+
 bool host_batch_device_ok(const sm_app* a) {
   if (!app_device_ok(a)) return false;
   for (auto& st : a->streams)
@@ -2676,8 +2728,8 @@ void flush(sm_app* a);
 
 // InputHandler.send(Event[]) (InputHandler.java:64-68) of a large columnar batch (sm_input_send_columns, at least
 // bulk_min events, no nulls, no STRING attribute) for an app whose queries all take the device-batch path
-// (app_device_ok): the columns go from the caller's memory straight to the device in chunks of bulk_chunk events,
-// without host staging, and each chunk runs through device_batch_stream with the next arrival ordinals (one carry, so
+// (app_bulk_device_ok): the columns go from the caller's memory straight to the device in chunks of bulk_chunk
+// events, without host staging, and each chunk runs through device_batch_stream with the next arrival ordinals (one carry, so
 // partials span the chunks as they span sends in the reference). A helper thread uploads chunk c + 1 on its own HIP
 // stream while chunk c is processed. Each chunk is processed under the app lock and its outputs go to the callbacks
 // before the next chunk (with the lock released, so a callback may send into the app: what it sends is staged and
@@ -2820,7 +2872,7 @@ void flush(sm_app* a) {
     // over first (nfa_device_batch without new events replays them into the NFA state) and stays on the NFA
     for (size_t qi = 0; qi < a->queries.size(); ++qi) {
       QueryRt& q = *a->queries[qi];
-      if (!q.cq.fast_every_within || q.nfa_mode || q.nfa_used || q.carry.n == 0) continue;
+      if (!closed_form(q.cq) || q.nfa_mode || q.nfa_used || q.carry.n == 0) continue;
       const int s = q.cq.streams.at(0);
       if (a->streams[s].rows > 0) nfa_device_batch(a, (int)qi, s, 0, nullptr, nullptr, nullptr, 0, a->stream, nullptr);
     }
@@ -3100,7 +3152,7 @@ int sm_input_send_columns(sm_input* in, size_t n, const int64_t* ts, const void*
       nulls |= null_flags && null_flags[k];
       strings |= (int)st.def->attrs[k].type == T_STRING;
     }
-    bulk = (int64_t)n >= a->bulk_min && !nulls && !strings && !a->bulk_active && app_device_ok(a);
+    bulk = (int64_t)n >= a->bulk_min && !nulls && !strings && !a->bulk_active && app_bulk_device_ok(a);
     if (bulk) {
       a->bulk_active = true;
       return;

@@ -1,0 +1,136 @@
+"""Benchmark of the adjacent-pair closed form of `every e1=S[c1], e2=S[c2] within T` (fast_path 6, kernels/seqpath.hip)
+on the config-4 data shape (bench.gen_stock: splitmix64 stream, f64 price, inputs resident on the device), keyed and
+unkeyed, against the only device route such a query had before: sm_app_process_device_events (the general NFA kernel,
+query-specialised JIT on). One JSON line per (route, form): ms per step (min / median / max over --steps timed steps
+after --warmup), events/s of the median step, outputs, and for the closed form the per-kernel times of option
+fast_timing. Each step starts from a fresh runtime state (option reset), as bench.py's steps do.
+
+    python tools/seq_bench.py --route closed            # the new kernels
+    python tools/seq_bench.py --route nfa               # the NFA route (run it with the parent commit's library too)
+    python tools/seq_bench.py --precompile              # CPU only: the NFA route's JIT kernels into the code cache
+
+Step time is a host clock around work that ends in a device synchronise; a run without a GPU fails."""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import bench  # noqa: E402
+
+SCHEMA = "define stream StockStream (symbol int, price double, volume long, timestamp long); "
+QUERY = ("@info(name='q') from every e1=StockStream[price>20], e2=StockStream[price>e1.price] within 1 sec "
+         "select e1.timestamp as i, e2.timestamp as j insert into OutputStream;")
+APPS = {
+    "keyed": SCHEMA + "partition with (symbol of StockStream) begin " + QUERY + " end;",
+    "unkeyed": SCHEMA + QUERY,
+}
+LABELS = ["seq_facts", "seq_sort", "seq_link", "seq_keep", "seq_count", "seq_scan", "seq_emit", "seq_carry"]
+
+
+def precompile():
+    """The NFA route's query-specialised kernels take minutes through hiprtc: compiled here, on a host without a GPU,
+    into siddhi_amd/jit_cache (the compact lane-event form a 4-attribute stream takes), one process per plan."""
+    import subprocess
+    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--precompile-one", form],
+                              env=dict(os.environ, SM_NFA_JIT_COMPACT="1")) for form in APPS]
+    sys.exit(max(p.wait() for p in procs))
+
+
+def precompile_one(form):
+    import torch  # noqa: F401  (first, as in every run: the library then compiles with the hiprtc torch bundles)
+    from siddhi_amd import _lib
+    log = ctypes.create_string_buffer(8192)
+    size = ctypes.c_size_t()
+    t = time.time()
+    rc = _lib.lib().sm_nfa_jit_compile(APPS[form].encode(), 0, log, 8192, ctypes.byref(size))
+    print(f"{form}: rc {rc}, {size.value} bytes, {time.time() - t:.0f} s {log.value.decode()[:200]}", flush=True)
+    sys.exit(rc)
+
+
+def stats(ms):
+    s = sorted(ms)
+    return {"min": s[0], "median": s[len(s) // 2], "max": s[-1]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--events", type=float, default=1e8)
+    ap.add_argument("--keys", type=int, default=1_000_000)
+    ap.add_argument("--ts-div", type=int, default=10_000)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--route", choices=["closed", "nfa"], default="closed")
+    ap.add_argument("--forms", default="keyed,unkeyed")
+    ap.add_argument("--precompile", action="store_true")
+    ap.add_argument("--precompile-one")
+    a = ap.parse_args()
+    if a.precompile_one:
+        precompile_one(a.precompile_one)
+    if a.precompile:
+        precompile()
+    if a.steps < 10:
+        print("note: fewer than 10 timed steps", file=sys.stderr)
+
+    import torch
+    from siddhi_amd import _lib
+    from siddhi_amd.testing import ProductApp
+    if not torch.cuda.is_available():
+        sys.exit("seq_bench needs a GPU")
+    dev = torch.device("cuda", 0)
+    n = int(a.events)
+    sym, price, _, _, ts = bench.gen_stock(0, n, a.keys, a.ts_div, dev, bench.seed_for(4))
+    ordinals = torch.arange(n, dtype=torch.int64, device=dev)  # the timestamp attribute = the event's ordinal
+    sidx = torch.zeros(n, dtype=torch.int32, device=dev) if a.route == "nfa" else None
+    hs = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    build_id = _lib.lib().sm_build_id().decode()
+    torch.cuda.synchronize()
+    for form in a.forms.split(","):
+        opts = {"nfa_jit": 1} if a.route == "nfa" else {}
+        app = ProductApp(APPS[form], **opts)
+        app.set_collect(False)
+        cols = [sym, price, price, ordinals]  # volume is not read: aliased
+
+        def step():
+            if a.route == "nfa":
+                app.set_option("reset", 1)
+                app.process_device_events(sidx, ts, cols, ordinals=ordinals, hip_stream=hs)
+            else:
+                app.set_option("reset", 0)
+                app.process_device_batch("StockStream", ts, cols, hip_stream=hs)
+            return int(app.get_stat("output_events:q"))
+
+        for _ in range(a.warmup):
+            step()
+        if a.route == "closed":
+            app.set_option("fast_timing", 1)
+        ms, kern, m = [], {}, 0
+        for _ in range(a.steps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            m = step()
+            torch.cuda.synchronize()
+            ms.append((time.perf_counter() - t0) * 1e3)
+            print(f"{a.route} {form} step {len(ms)}: {ms[-1]:.3f} ms", file=sys.stderr, flush=True)
+            if a.route == "closed":
+                for lab in LABELS:
+                    if app.get_stat("kernel_calls:" + lab):
+                        kern.setdefault(lab, []).append(app.get_stat("kernel_ms:" + lab))
+        st = stats(ms)
+        line = {"route": a.route, "form": form, "events": n, "keys": a.keys, "ts_div": a.ts_div, "steps": a.steps,
+                "warmup": a.warmup, "ms": st, "events_per_s": n / (st["median"] * 1e-3), "outputs": m,
+                "build_id": build_id}
+        if a.route == "closed":
+            line["fast_path"] = int(app.get_stat("fast_path:q"))
+            line["kernel_ms_median"] = {k: sorted(v)[len(v) // 2] for k, v in kern.items()}
+        else:
+            line["nfa_kernel"] = int(app.get_stat("nfa_kernel:q"))
+        print(json.dumps(line), flush=True)
+        app.close()
+
+
+if __name__ == "__main__":
+    main()
