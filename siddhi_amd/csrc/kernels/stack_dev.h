@@ -4,6 +4,10 @@
 // plain per-key pending-list model on the CPU.
 #pragma once
 #include "fastpath_dev.h"
+#ifdef SM_HOST_EMU
+#include <cstdio>
+#include <cstdlib>
+#endif
 
 namespace sm {
 namespace {
@@ -158,6 +162,25 @@ __device__ __forceinline__ void st_push(Stack& s, uint4* sp, uint32_t o, uint32_
   ++s.n;
 }
 
+// Sentinel padding of the register stack (ring kernel v4; v2 does not pad): entries at index >= n hold a code no event
+// beats unless it beats every live entry too (the largest code for > and >=, the smallest for < and <=), and a time
+// no event of the batch finds expired (event times are below 2^30 relative to the batch), so that the event step's
+// compares need no `u < n` test.
+constexpr int32_t kPadT = 1 << 30;
+template <int OP>
+__device__ __forceinline__ constexpr uint32_t pad_code() {
+  return (OP == CMP_LT || OP == CMP_LE) ? 0u : 0xffffffffu;
+}
+template <int OP>
+__device__ __forceinline__ void st_pad(Stack& s) {
+#pragma unroll
+  for (int k = 0; k < kC; ++k)
+    if (k >= s.n) {
+      s.c[k] = pad_code<OP>();
+      s.t[k] = kPadT;
+    }
+}
+
 // block-wide exclusive scan of one value per thread (NT threads); returns the total through *tot
 template <int NT = kOB>
 __device__ __forceinline__ uint32_t block_excl(uint32_t v, uint32_t* lw, uint32_t* tot) {
@@ -261,6 +284,9 @@ struct Stack4Args {
 
 #ifndef SM_STACK4_SKIP
 #define SM_STACK4_SKIP 0  // diagnostic build flag: 1 = no event loop (every pop count 0; wrong results, timing only)
+#endif
+#ifndef SM_STACK4_FLAT
+#define SM_STACK4_FLAT 1  // A/B build flag: 0 = every event takes the general (cold) step of the event loop
 #endif
 #ifndef SM_STACK4_STAMPS
 #define SM_STACK4_STAMPS 0  // diagnostic build flag: phase clock of stack4_kernel (0 rank, 1 stacks, 2 wait, 3 emit, 4 rest)
@@ -376,6 +402,25 @@ __device__ SM_RANK4_INLINE void rank4(Slot4& S, const uint4 (&pre)[kI4], int sn,
   lds_barrier();
 }
 
+#ifdef SM_HOST_EMU
+// emulator build only: what the straight-line event step relies on, for an event (cj, jt) without a tie
+template <int OP>
+inline void sm4_check_step(const Stack& st, uint32_t cj, int32_t jt, int32_t weff, int nhit, int nexp) {
+  bool ok = st.n >= 0 && st.n <= kC && nexp <= st.n;
+  for (int u = 0; u < kC; ++u) {
+    if (u >= st.n) ok = ok && st.c[u] == pad_code<OP>() && st.t[u] == kPadT;  // padded
+    ok = ok && cmp_fixed<OP>(cj, st.c[u]) == (u < nhit);                       // c2 holds on a prefix
+    ok = ok && (jt - st.t[u] > weff) == (u >= st.n - nexp && u < st.n);        // expired is a suffix of the live
+    if (u > 0 && u < st.n) ok = ok && st.t[u] <= st.t[u - 1];                  // older towards the bottom
+  }
+  if (!ok) {
+    fprintf(stderr, "stack4 event step: invariant broken (n %d, nhit %d, nexp %d, code %u, time %d)\n", st.n, nhit,
+            nexp, cj, jt);
+    abort();
+  }
+}
+#endif
+
 template <int OP, bool FP>
 __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
   __shared__ __attribute__((aligned(16))) Slot4 sl[kR];
@@ -386,6 +431,7 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
   const int h = tid;
   const bool has = h < a.H;
   const int32_t within32 = a.within;
+  const int32_t weff = within32 < 0 ? INT32_MAX : within32;  // no `within`: no difference of two times exceeds it
   uint4* sp = a.spill + ((int64_t)blockIdx.x * kKeys + h) * kQ;
   unsigned long long st_acc[5] = {0, 0, 0, 0, 0}, st_last = SM4_CLOCK();
 
@@ -399,6 +445,8 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
     const uint32_t kr = ((uint32_t)h << kRB) | (uint32_t)d;
     Stack st;
     st.n = st.hb = st.hn = 0;
+#pragma unroll
+    for (int k = 0; k < kC; ++k) st.o[k] = 0;  // (ordinals at index >= n are never used; defined all the same)
     uint32_t cs = 0, ce = 0;
     if (has && a.cold->cin) {  // carried partials first (oldest first)
       const Stack4Cold* c4 = a.cold;
@@ -409,6 +457,7 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
         st_push(st, sp, c.x, c.y, (int32_t)c.z, (int32_t)c.z, within32, a.err);
       }
     }
+    st_pad<OP>(st);
     int32_t tl = 0;
     bool seen = false;
     uint32_t mrun = 0;
@@ -448,36 +497,184 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
     for (uint32_t e = 0; e < nsl; ++e) {
       const int q0 = (int)(e % kR);
       // ---- stack phase: finish this lane's events of slice e; go on into the later held slices meanwhile
-      while (!SM_STACK4_SKIP && __any(cnt[0] != 0)) {
+      // (a loop with its test at the bottom: the compiler does not rotate a loop whose test is a wave vote, and with
+      // the test at the top it copies the whole register stack at the loop's head in every iteration)
+      if (!SM_STACK4_SKIP && __any(cnt[0] != 0)) do {
         // the lane's next event: its first held slice with events left
         int k = kR - 1;
-#pragma unroll
-        for (int u = kR - 2; u >= 0; --u)
-          if (cnt[u]) k = u;
         uint32_t o_ = off[kR - 1], c_ = cnt[kR - 1];
+        if constexpr (kR == 2) {  // plain selects
+          k = cnt[0] != 0 ? 0 : 1;
+          o_ = k ? off[1] : off[0];
+          c_ = k ? cnt[1] : cnt[0];
+        } else {
 #pragma unroll
-        for (int u = kR - 2; u >= 0; --u)
-          if (u == k) {
-            o_ = off[u];
-            c_ = cnt[u];
-          }
-        if (c_ != 0) {  // else nothing is held for this lane: it waits for the wave
+          for (int u = kR - 2; u >= 0; --u)
+            if (cnt[u]) k = u;
 #pragma unroll
-        for (int u = 0; u < kR; ++u)
-          if (u == k) {
-            off[u] = o_ + 1;
-            cnt[u] = c_ - 1;
-          }
+          for (int u = kR - 2; u >= 0; --u)
+            if (u == k) {
+              o_ = off[u];
+              c_ = cnt[u];
+            }
+        }
+        // act: the lane has an event; else nothing is held for it and it waits for the wave. Such a lane runs the
+        // straight-line step too, on its slot's first record and with every effect masked: a step under `if (act)`
+        // would leave the compiler two versions of the register stack to merge, which it does with a copy of all of
+        // it per iteration.
+        const bool act = c_ != 0;
+        if constexpr (kR == 2) {
+          const uint32_t a0 = k == 0 ? 1u : 0u, a1 = ((k != 0) & act) ? 1u : 0u;
+          off[0] += a0;
+          cnt[0] -= a0;
+          off[1] += a1;
+          cnt[1] -= a1;
+        } else {
+#pragma unroll
+          for (int u = 0; u < kR; ++u)
+            if ((u == k) & act) {
+              off[u] = o_ + 1;
+              cnt[u] = c_ - 1;
+            }
+        }
         const int q = q0 + k >= kR ? q0 + k - kR : q0 + k;
         Slot4& S = sl[q];
-        const uint2 g = S.grp[o_];
-        const uint32_t ep = S.epos[o_];
-        const uint32_t p = ep & 0x7fffu;
+        const uint32_t oa = act ? o_ : 0u;
+        const uint2 g = S.grp[oa];
+        const uint32_t ep = S.epos[oa];
+        const uint32_t p = act ? ep & 0x7fffu : 0u;
+        const uint32_t oj = S.ordt[p];
+        const bool push = (ep >> 15) != 0;
         const uint32_t cj = g.x;
         const int32_t jt = (int32_t)g.y;
-        tl = jt;
-        seen = true;
-        // a NaN anywhere sent the batch to the sort / walk kernels (rank4: SE_NAN), so the codes alone decide here
+        tl = act ? jt : tl;
+        seen |= act;
+        // a NaN anywhere sent the batch to the sort / walk kernels (rank4: SE_NAN), so the codes alone decide here.
+        //
+        // Straight-line step. The register stack is padded (st_pad) and, for the four ordered compares, monotone: from
+        // the top the codes never get easier to beat and the times never get younger (events of a key arrive in time
+        // order; a push follows the pops of everything the new entry beats). So without a tie of inexact codes "c2
+        // holds" is a prefix of the entries and "expired" is a suffix of the live ones, and the run is two counts:
+        //   nhit = entries the event's code beats (a padded entry only together with every live one),
+        //   nexp = expired entries (never a padded one), nl = n - nexp,
+        //   pops = min(nhit, nl); the run stopped at an expired entry, which clears the stack, iff nexp && nl <= nhit.
+        // The new stack is the old one shifted by pops with padding coming in at the bottom (a barrel shift written as
+        // selects), then shifted the other way by one under the event's entry if c1 holds: no branch, no exec region.
+        // A tie of inexact codes and a spill onto a full ring take the general step below.
+        int nhit = 0, nexp = 0;
+        bool anytie = false;
+#pragma unroll
+        for (int u = 0; u < kC; ++u) {
+          nhit += cmp_fixed<OP>(cj, st.c[u]) ? 1 : 0;
+          nexp += jt - st.t[u] > weff ? 1 : 0;
+          anytie |= st.c[u] == cj;
+        }
+        const int nl = st.n - nexp;
+        const int nmin = nhit < nl ? nhit : nl;
+        const bool clr = (nexp != 0) & (nl <= nhit);
+        const int nrem = clr ? 0 : st.n - nmin;
+        // A push onto a full stack stays here: the push shift drops the bottom entry. If that entry has expired, so has
+        // the spill ring, which is emptied (it is how expired entries leave a stack that no run reaches); if it is
+        // live, it is stored to the ring first (no wait: the store is not read back before a refill, which waits).
+        // A run through all of the registers with entries left in the ring is finished below, after the step.
+        const bool full = push & (nrem == kC);
+        const bool spill = full & (nexp == 0), refill = (nexp == 0) & (nhit >= st.n) & (st.hn > 0);
+        const bool general = !SM_STACK4_FLAT | (anytie & !a.exact_codes) | (spill & (st.hn == kQ));
+        const bool flat = act & !general;
+#ifdef SM_HOST_EMU
+        if (flat) sm4_check_step<OP>(st, cj, jt, weff, nhit, nexp);
+#endif
+        const uint32_t np = flat ? (uint32_t)nmin : 0u;
+        const bool clear = flat & clr, pushf = flat & push, ring0 = flat & (clr | (full & !spill));
+        if (flat & spill) {
+          sp[(st.hb + st.hn) & (kQ - 1)] = make_uint4(st.o[kC - 1], st.c[kC - 1], (uint32_t)st.t[kC - 1], 0u);
+          ++st.hn;
+        }
+        if (np) S.pk[p] = st.o[0];
+        if (np > 1) {  // further pops go to the slot's pool
+          const uint32_t base = atomicAdd(&s_pool[q], np - 1u);
+          if (base + np - 1u > (uint32_t)kPool) atomicOr(a.err, SE_LOG);
+#pragma unroll
+          for (int u = 1; u < kC; ++u)
+            if ((uint32_t)u < np && base + u - 1u < (uint32_t)kPool)
+              S.pool[base + u - 1u] = make_uint2(st.o[u], p | ((uint32_t)u << 16));
+        }
+        if (flat) S.jc[p] = (uint8_t)np;
+        {
+          // the old entries move up by the pops (a cleared stack: by all of them), padding comes in at the bottom ...
+          constexpr int top = kC >= 8 ? 8 : kC >= 4 ? 4 : 2;
+          static_assert(kC < 2 * top, "the shift's bits cover kC");
+          const uint32_t sh = clear ? (uint32_t)kC : np;
+#pragma unroll
+          for (int b = top; b >= 1; b >>= 1) {
+            const bool on = (sh & (uint32_t)b) != 0;
+#pragma unroll
+            for (int u = 0; u < kC; ++u) {  // ascending: entry u + b is still the previous stage's
+              if (u + b < kC) {
+                st.o[u] = on ? st.o[u + b] : st.o[u];
+                st.c[u] = on ? st.c[u + b] : st.c[u];
+                st.t[u] = on ? st.t[u + b] : st.t[u];
+              } else {  // (the ordinal of a padded entry is never used)
+                st.c[u] = on ? pad_code<OP>() : st.c[u];
+                st.t[u] = on ? kPadT : st.t[u];
+              }
+            }
+          }
+          // ... and this event's entry goes on top (the bottom entry it pushes out is padding, or expired)
+#pragma unroll
+          for (int u = kC - 1; u > 0; --u) {
+            st.o[u] = pushf ? st.o[u - 1] : st.o[u];
+            st.c[u] = pushf ? st.c[u - 1] : st.c[u];
+            st.t[u] = pushf ? st.t[u - 1] : st.t[u];
+          }
+          st.o[0] = pushf ? oj : st.o[0];
+          st.c[0] = pushf ? cj : st.c[0];
+          st.t[0] = pushf ? jt : st.t[0];
+          st.n = flat ? nrem + ((push & !full) ? 1 : 0) : st.n;
+          st.hn = ring0 ? 0 : st.hn;
+        }
+        if (__builtin_expect(flat & refill, 0)) {
+          // The run popped every register entry and the ring is not empty: it goes on there, youngest first, one
+          // entry at a time (rare). An entry that stays comes back into the registers, beneath this event's own.
+          uint32_t npop = np;
+#pragma unroll 1
+          for (;;) {
+            const uint4 e = sp[(st.hb + st.hn - 1) & (kQ - 1)];
+            if (jt - (int32_t)e.z > weff) {  // expired: so is everything older
+              st.hn = 0;
+              break;
+            }
+            const bool hh = (a.exact_codes | (e.y != cj)) ? cmp_fixed<OP>(cj, e.y)
+                                                          : c2_exact4<OP, FP>(a.cold, cs, ce, e.x, oj);
+            st.hn -= 1;
+            if (!hh) {
+              if (push) {
+                st.o[1] = e.x;
+                st.c[1] = e.y;
+                st.t[1] = (int32_t)e.z;
+              } else {
+                st.o[0] = e.x;
+                st.c[0] = e.y;
+                st.t[0] = (int32_t)e.z;
+              }
+              st.n += 1;
+              break;
+            }
+            if (npop == 0) {
+              S.pk[p] = e.x;
+            } else {  // each spilled pop reserves its own pool entry
+              const uint32_t b1 = atomicAdd(&s_pool[q], 1u);
+              if (b1 < (uint32_t)kPool) S.pool[b1] = make_uint2(e.x, p | (npop << 16));
+              else atomicOr(a.err, SE_LOG);
+            }
+            ++npop;
+            if (st.hn == 0) break;
+          }
+          S.jc[p] = (uint8_t)npop;
+        }
+        if (__builtin_expect(act & general, 0)) {
+        // General step (rare: a tie of inexact codes, a spill onto a full ring): per-entry masks with the live test,
+        // the exact compare of tied codes, refills from the spill ring, st_push; the padding is restored at its end.
         uint32_t hit = 0, exp = 0, tie = 0;
 #pragma unroll
         for (int u = 0; u < kC; ++u) {
@@ -487,7 +684,6 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
           tie |= (lv && !a.exact_codes && st.c[u] == cj) ? (1u << u) : 0u;
         }
         if (tie) {  // equal inexact codes: the exact values decide (out of line, one call site)
-          const uint32_t oj = S.ordt[p];
 #pragma unroll 1
           for (uint32_t m = tie; m; m &= m - 1u) {
             const int u = __builtin_ctz(m);
@@ -539,7 +735,7 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
               break;
             }
             const bool hh = (a.exact_codes | (st.c[0] != cj)) ? cmp_fixed<OP>(cj, st.c[0])
-                                                               : c2_exact4<OP, FP>(a.cold, cs, ce, st.o[0], S.ordt[p]);
+                                                               : c2_exact4<OP, FP>(a.cold, cs, ce, st.o[0], oj);
             if (!hh) break;
             if (npop == 0) {
               S.pk[p] = st.o[0];
@@ -554,9 +750,10 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
           }
         }
         S.jc[p] = (uint8_t)npop;
-        if (ep >> 15) st_push(st, sp, S.ordt[p], cj, jt, jt, within32, a.err);
+        if (push) st_push(st, sp, oj, cj, jt, jt, within32, a.err);
+        st_pad<OP>(st);
         }
-      }
+      } while (__any(cnt[0] != 0));
       SM4_PHASE(1);
       lds_barrier();  // every lane is done with slice e
       SM4_PHASE(2);
