@@ -303,11 +303,7 @@ __global__ void __launch_bounds__(256) scan_chunks_kernel(uint32_t* __restrict__
   for (int b = 0; b < G; b += 256) {
     const int g = b + threadIdx.x;
     const uint32_t v = g < G ? row[g] : 0u;
-    uint32_t inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t u = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += u;
-    }
+    const uint32_t inc = wave_incl_scan(v);
     if (lane == 63) lw[w] = inc;
     __syncthreads();
     uint32_t run = carry + inc - v;
@@ -330,11 +326,7 @@ __global__ void __launch_bounds__(kBlock) digit_base_kernel(uint32_t* __restrict
     s += v[k];
   }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t inc = s;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t u = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += u;
-  }
+  const uint32_t inc = wave_incl_scan(s);
   if (lane == 63) lw[w] = inc;
   __syncthreads();
   uint32_t run = inc - s;
@@ -556,11 +548,7 @@ downsweep_kernel(Src src, uint4* __restrict__ drec, uint64_t* __restrict__ dpair
       csum += r;
     }
     {  // block exclusive scan of the tile counts over digits → tstart
-      uint32_t inc = csum;
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += u;
-      }
+      const uint32_t inc = wave_incl_scan(csum);
       if (lane == 63) lw[w] = inc;
       lds_barrier();
       uint32_t r = inc - csum;
@@ -734,11 +722,7 @@ downsweep_wc_kernel(Src src, uint4* __restrict__ drec, uint64_t* __restrict__ dp
       csum += r;
     }
     {  // block exclusive scan of the tile counts over digits → tstart
-      uint32_t inc = csum;
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += u;
-      }
+      const uint32_t inc = wave_incl_scan(csum);
       if (lane == 63) lw[w] = inc;
       lds_barrier();
       uint32_t r = inc - csum;
@@ -1158,11 +1142,7 @@ __global__ void __launch_bounds__(kWalkBlock) __attribute__((amdgpu_waves_per_eu
     // carry out: partials still pending at the end of the batch (wave-aggregated append)
     if (__any(pendm != 0)) {
       const uint32_t np = (uint32_t)__popc(pendm);
-      uint32_t inc = np;
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t u = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += u;
-      }
+      const uint32_t inc = wave_incl_scan(np);
       uint32_t cb = 0;
       if (lane == 63 && inc) cb = atomicAdd(a.cand_n, inc);
       cb = __shfl(cb, 63, 64) + inc - np;
@@ -1486,12 +1466,7 @@ __global__ void __launch_bounds__(kJtThreads) jt_place_kernel(const uint64_t* __
       for (int v = 0; v < kJtW; ++v) tot[x] += cw[v][jo];
       s += tot[x];
     }
-    uint32_t inc = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t u = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += u;
-    }
+    const uint32_t inc = wave_incl_scan(s);
     if (lane == 63) wsum[w] = inc;
     lds_barrier();
     uint32_t base = inc - s;

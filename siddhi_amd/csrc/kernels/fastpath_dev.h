@@ -116,6 +116,68 @@ __device__ __forceinline__ int wave_index() {
 #endif
 }
 
+// One v_mov_b32_dpp, bank mask 0xf, bound_ctrl off: the lane takes v of the lane CTRL names, or keeps `old` where
+// that lane does not exist or the lane's own 16-lane row is not in the row mask ROWS. Only the three controls of
+// the scans below are used (and modelled by the host wave emulator, hd.h sm_emu_dpp).
+constexpr int kDppRowShr = 0x110;      // row_shr:n = kDppRowShr + n: lane l - n of the same row
+constexpr int kDppRowBcast15 = 0x142;  // row_bcast:15: lane 15 of the row before
+constexpr int kDppRowBcast31 = 0x143;  // row_bcast:31: lane 31, into rows 2 and 3
+template <int CTRL, int ROWS>
+__device__ __forceinline__ uint32_t sm_dpp(uint32_t old, uint32_t v) {
+#if !defined(__HIP_DEVICE_COMPILE__) && defined(SM_HOST_EMU)
+  return sm_emu_dpp(old, v, CTRL, ROWS);
+#else
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)old, (int)v, CTRL, ROWS, 0xf, false);
+#endif
+}
+
+// v of lane l, l wave-uniform (v_readlane)
+__device__ __forceinline__ uint32_t wave_read_lane(uint32_t v, int l) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, l);
+#else
+  return __shfl(v, l, 64);
+#endif
+}
+
+// Inclusive scan within each 16-lane row: four DPP adds, no LDS and no lane masks (with old = 0 the compiler folds
+// each move into the add: v_add_u32_dpp). Every lane of the wave must be active: an inactive lane contributes 0
+// and not its register, unlike a __shfl_up.
+__device__ __forceinline__ uint32_t row_incl_scan(uint32_t v) {
+  v += sm_dpp<kDppRowShr + 1, 0xf>(0u, v);
+  v += sm_dpp<kDppRowShr + 2, 0xf>(0u, v);
+  v += sm_dpp<kDppRowShr + 4, 0xf>(0u, v);
+  v += sm_dpp<kDppRowShr + 8, 0xf>(0u, v);
+  return v;
+}
+
+// Inclusive scan over the 64 lanes of the wave: the row scan, then lane 15 of rows 0 and 2 into rows 1 and 3, then
+// lane 31 into rows 2 and 3. Precondition: every lane of the wave is active (all call sites are block-uniform).
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
+  v = row_incl_scan(v);
+  v += sm_dpp<kDppRowBcast15, 0xa>(0u, v);
+  v += sm_dpp<kDppRowBcast31, 0xc>(0u, v);
+  return v;
+}
+
+// Block-wide exclusive scan of one value per thread (NT threads, a multiple of 64, at most 1024; the default is the
+// workgroup of the order kernels); returns the total through *tot. lw: NT / 64 words of LDS. One barrier inside,
+// between the write of lw and its reads: the caller fences lw's reuse (a barrier between two scans on the same lw).
+// The wave totals are scanned by every wave alike, in one 16-lane row (lane l holds wave l & 15).
+template <int NT = 1024>
+__device__ __forceinline__ uint32_t block_excl(uint32_t v, uint32_t* lw, uint32_t* tot) {
+  static_assert(NT % 64 == 0 && NT / 64 >= 1 && NT / 64 <= 16, "the wave totals fit one 16-lane row");
+  const int lane = threadIdx.x & 63, w = wave_index();
+  const uint32_t inc = wave_incl_scan(v);
+  if (lane == 63) lw[w] = inc;
+  lds_barrier();
+  const int q = lane & 15;
+  const uint32_t ws = row_incl_scan(q < NT / 64 ? lw[q] : 0u);
+  const uint32_t before = wave_read_lane(ws, w > 0 ? w - 1 : 0);
+  *tot = wave_read_lane(ws, NT / 64 - 1);
+  return inc - v + (w > 0 ? before : 0u);
+}
+
 __device__ __forceinline__ StackVal col_value(const NfaStream* st, int a, int64_t row) {
   StackVal v;
   v.i = 0;

@@ -100,6 +100,25 @@ inline T __shfl_up(T v, unsigned d, int = 64) {
   const T r = sm_emu_exchange(v, l >= (int)d ? l - (int)d : l);
   return l >= (int)d ? r : v;
 }
+// v_mov_b32_dpp with bank mask 0xf and bound_ctrl off, for the three controls of the wave scans (fastpath_dev.h):
+// row_shr:n (0x111 .. 0x11f; lane l - n of the same 16-lane row, none for the row's first n lanes), row_bcast:15
+// (0x142; lane 15 of the row before, none for row 0) and row_bcast:31 (0x143; lane 31, for rows 2 and 3). A lane
+// without a source lane, or whose row is not in row_mask, keeps `old`.
+inline unsigned sm_emu_dpp(unsigned old, unsigned v, int ctrl, unsigned row_mask) {
+  const int l = sm_emu::lane(), row = l >> 4;
+  int src = -1;
+  if (ctrl > 0x110 && ctrl <= 0x11f) {
+    if ((l & 15) >= (ctrl & 15)) src = l - (ctrl & 15);
+  } else if (ctrl == 0x142) {
+    if (row > 0) src = row * 16 - 1;
+  } else if (ctrl == 0x143) {
+    if (row >= 2) src = 31;
+  } else {
+    __builtin_trap();  // a control this model does not know
+  }
+  const unsigned r = sm_emu_exchange(v, src < 0 ? l : src);
+  return src >= 0 && ((row_mask >> row) & 1u) ? r : old;
+}
 inline int __popcll(unsigned long long x) { return __builtin_popcountll(x); }
 inline int __popc(unsigned x) { return __builtin_popcount(x); }
 inline unsigned atomicAdd(unsigned* p, unsigned v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }

@@ -30,27 +30,6 @@ __device__ __forceinline__ uint32_t sm_udot2(uint32_t a, uint32_t b, uint32_t c)
 #endif
 }
 
-// block-wide exclusive scan of one value per thread; the total through *tot
-__device__ __forceinline__ uint32_t p0_block_excl(uint32_t v, uint32_t* lw, uint32_t* tot) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t u = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += u;
-  }
-  if (lane == 63) lw[w] = inc;
-  lds_barrier();
-  uint32_t r = inc - v, t = 0;
-  for (int q = 0; q < kP0Waves; ++q) {
-    const uint32_t x = lw[q];
-    if (q < w) r += x;
-    t += x;
-  }
-  *tot = t;
-  return r;
-}
-
 // sum of the u16 counts of waves [0, w) in a digit's row (8 words, two waves each)
 __device__ __forceinline__ uint32_t p0_before(const uint4& r0, const uint4& r1, int w) {
   const uint32_t word[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
@@ -147,7 +126,14 @@ __global__ void __launch_bounds__(kP0Block) pass0_kernel(Src src, uint4* __restr
     const int tile_n = (int)((end - base) < kP0Tile ? (end - base) : kP0Tile);
     const bool last = base + kP0Tile >= end;
     uint4 rec[kP0Items];
-    if (more) {  // the loop's only wait for vector memory
+    // The loop's only wait for vector memory: vmcnt(0), stated once and under no condition. The waits the compiler
+    // places itself sit under `more` and `e < tile_n` and leave it, on paths no tile takes, a load still in flight
+    // into raw[]'s registers; it then guards every address it forms in one of them at load_tile with a wait of its
+    // own, behind this tile's stores and between the tile's loads.
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+#endif
+    if (more) {
 #pragma unroll
       for (int k = 0; k < kP0Items; ++k) {
         const int e = w * 64 * kP0Items + k * 64 + lane;
@@ -218,7 +204,7 @@ __global__ void __launch_bounds__(kP0Block) pass0_kernel(Src src, uint4* __restr
 #pragma unroll
       for (int i = 0; i < 8; ++i) ct = sm_udot2(word[i], 0x00010001u, ct);
       uint32_t tot;
-      tstart[tid] = p0_block_excl(ct, lw, &tot);
+      tstart[tid] = block_excl<kP0Block>(ct, lw, &tot);
       if (tid == 0) tstart[kBins] = tot;
     }
     const uint32_t rn = run[tid], c0 = cst[tid];

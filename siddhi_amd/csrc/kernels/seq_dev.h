@@ -221,11 +221,7 @@ __global__ void __launch_bounds__(kSeqBlock) seq_emit_kernel(const int32_t* __re
   seq_load_items(e1, r0, n, v);
   uint32_t c = 0;
   for (int k = 0; k < kSeqItems; ++k) c += v[k] != kSeqNone;
-  uint32_t inc = c;
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t x = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += x;
-  }
+  const uint32_t inc = wave_incl_scan(c);
   if (lane == 63) wsum[w] = inc;
   lds_barrier();
   uint32_t p = offsets[blockIdx.x] + inc - c;

@@ -446,12 +446,7 @@ __global__ void __launch_bounds__(kSB) stack_kernel(StackArgs a) {
     const uint32_t keepA = hasA ? keep_of(sA, spA, tlA, seenA) : 0u;
     const uint32_t keepB = hasB ? keep_of(sB, spB, tlB, seenB) : 0u;
     const uint32_t keep = keepA + keepB;
-    uint32_t inc = keep;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t u = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += u;
-    }
+    const uint32_t inc = wave_incl_scan(keep);
     uint32_t base = 0;
     if (lane == 63 && inc) base = atomicAdd(a.cand_n, inc);
     base = __shfl(base, 63, 64) + inc - keep;

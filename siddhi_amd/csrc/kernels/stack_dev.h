@@ -181,27 +181,7 @@ __device__ __forceinline__ void st_pad(Stack& s) {
     }
 }
 
-// block-wide exclusive scan of one value per thread (NT threads); returns the total through *tot
-template <int NT = kOB>
-__device__ __forceinline__ uint32_t block_excl(uint32_t v, uint32_t* lw, uint32_t* tot) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t u = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += u;
-  }
-  if (lane == 63) lw[w] = inc;
-  lds_barrier();
-  uint32_t r = inc - v, t = 0;
-  for (int q = 0; q < NT / 64; ++q) {
-    const uint32_t x = lw[q];
-    if (q < w) r += x;
-    t += x;
-  }
-  *tot = t;
-  return r;
-}
+static_assert(kOB == 1024, "block_excl's default (fastpath_dev.h) is the order workgroup");
 
 // ============================================================================================================
 // v4 (default): the same closed form with a ring of ranked slices, so that no lane waits for the slowest key chain
@@ -849,12 +829,7 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
       for (int k = 0; k < st.hn; ++k)
         if (pending((int32_t)sp[(st.hb + k) & (kQ - 1)].z)) ++keep;
     }
-    uint32_t inc = keep;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t u = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += u;
-    }
+    const uint32_t inc = wave_incl_scan(keep);
     uint32_t base = 0;
     const Stack4Cold* c4 = a.cold;
     if (lane == 63 && inc) base = atomicAdd(c4->cand_n, inc);
