@@ -127,10 +127,15 @@ struct StackPlan {
   int64_t within;
   int64_t ts0, ts_last;
   int32_t o0;               // relative ordinal of the batch's first event: carried partials lie before it
+  // The pipeline's four status words, taken and zeroed by the caller before key pass 0 when that pass checks the
+  // time order (keys-only prep): pass 0 sets word 3 if event time decreases somewhere in the batch, and the pipeline
+  // reads it with its first read-back, before the stack kernel. nullptr: the pipeline takes its own.
+  uint32_t* status = nullptr;
 };
 
 // M >= 0, or -1 when the batch must take the sort / walk pipeline instead (a key's open partials overflowed the
 // stack, a slice's match log filled, a NaN compared value): neither pairs_out nor the carry was touched then.
+// FAST_NON_MONOTONE when p.status is given and key pass 0 found event time decreasing: nothing was touched either.
 int64_t stack_pipeline(const StackPlan& p, const FastArgs& a, const FastHostInfo& hi, FastState& fs, FastCarry& carry,
                        uint32_t* pairs_out, int64_t pairs_cap, Scratch& sc, hipStream_t s, FastTimings* tm);
 

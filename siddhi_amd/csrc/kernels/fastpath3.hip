@@ -5,7 +5,8 @@
 // Every pass is a reduce-then-scan pass over G persistent workgroups, each owning one contiguous chunk of the
 // input (no inter-workgroup waiting inside a launch: a decoupled look-back walks the status words of the
 // tiles still in flight one cross-XCD load at a time, which on MI355X cost more than the data movement):
-//   prep      key min/max, ts monotonicity + span, max relative ordinal, compared-attribute range
+//   prep      key min/max, ts monotonicity + span, max relative ordinal, compared-attribute range (config 4's
+//             shape: the key column alone, prep_keys_kernel; key pass 0 checks the time order)
 //   up_key    per-chunk digit counts of the rebased key (pass 0 from the key column, later passes from the
 //             records)
 //   scan      per digit, exclusive over chunks; digit bases                             (G x kBins counts)
@@ -28,6 +29,7 @@
 // comparison and equal codes (or NaN) fall back to the exact column values (rare; the record's ordinal gives
 // the row).
 #include <cstdlib>
+#include <limits>
 #include <type_traits>
 #include <vector>
 
@@ -249,6 +251,73 @@ __global__ void __launch_bounds__(kBlock) prep_kernel(const KT* __restrict__ kco
     for (int d = threadIdx.x; d < kBins; d += kBlock) cnt[(int64_t)d * G + blockIdx.x] = h[d];
 }
 
+// Keys-only prep: a keyed batch with no ordinal column, no LONG compared attribute and c1 evaluated in pass 0
+// (prep_kernel<KT, false, false>'s case) whose records pass0_kernel builds. The one question prep asked of the time
+// column, "is it non-decreasing", is answered by pass 0 from the timestamps it loads anyway (OrigSrc<.., true>,
+// pass0_dev.h), so this pass reads 4 of the 12 bytes per event: key min/max and the per-chunk digit counts, as
+// prep_kernel; ts0 / ts_last by one thread. Strided tiles of kKeyItems keys per thread, all loaded before the first
+// is used.
+constexpr int kKeyItems = 16;
+template <typename KT>
+__global__ void __launch_bounds__(kBlock) prep_keys_kernel(const KT* __restrict__ kcol, const int64_t* __restrict__ ts,
+                                                           int64_t n, int64_t per, int G, uint32_t* __restrict__ cnt,
+                                                           Ctrl* __restrict__ c) {
+  __shared__ uint32_t h[kBins];
+  for (int d = threadIdx.x; d < kBins; d += kBlock) h[d] = 0;
+  __syncthreads();
+  int64_t lo0, len;
+  chunk_range(blockIdx.x, n, per, nullptr, lo0, len);
+  const int64_t hi0 = lo0 + len;
+  KT kmn = std::numeric_limits<KT>::max(), kmx = std::numeric_limits<KT>::min();
+  for (int64_t base = lo0; base < hi0; base += (int64_t)kBlock * kKeyItems) {
+    KT kk[kKeyItems];
+#pragma unroll
+    for (int k = 0; k < kKeyItems; ++k) {
+      const int64_t p = base + k * kBlock + threadIdx.x;
+      if (p < hi0) kk[k] = __builtin_nontemporal_load(kcol + p);
+    }
+#pragma unroll
+    for (int k = 0; k < kKeyItems; ++k) {
+      const int64_t p = base + k * kBlock + threadIdx.x;
+      if (p < hi0) {
+        kmn = kmn < kk[k] ? kmn : kk[k];
+        kmx = kmx > kk[k] ? kmx : kk[k];
+        atomicAdd(&h[(uint32_t)kk[k] & (kBins - 1)], 1u);
+      }
+    }
+  }
+  const bool any = lo0 + (int64_t)threadIdx.x < hi0;  // this thread read a key
+  unsigned long long lo = any ? (unsigned long long)(int64_t)kmn ^ 0x8000000000000000ull : ~0ull;
+  unsigned long long hi = any ? (unsigned long long)(int64_t)kmx ^ 0x8000000000000000ull : 0ull;
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long x = __shfl_down(lo, o, 64), y = __shfl_down(hi, o, 64);
+    lo = x < lo ? x : lo;
+    hi = y > hi ? y : hi;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicMin(&c->kmin, lo);
+    atomicMax(&c->kmax, hi);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    c->ts0 = ts[0];
+    c->ts_last = ts[n - 1];
+    c->o0 = 0;
+    c->omax = (unsigned long long)(n - 1);
+  }
+  __syncthreads();
+  for (int d = threadIdx.x; d < kBins; d += kBlock) cnt[(int64_t)d * G + blockIdx.x] = h[d];
+}
+
+// The time-order question alone, for a batch that took the keys-only prep and leaves the fast path before pass 0
+// (key span, time span): the answer decides which way it leaves, as when prep gave it.
+__global__ void __launch_bounds__(256) ts_order_kernel(const int64_t* __restrict__ ts, int64_t n,
+                                                       Ctrl* __restrict__ c) {
+  bool bad = false;
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x + 1; p < n; p += (int64_t)gridDim.x * 256)
+    bad |= ts[p] < ts[p - 1];
+  if (bad) atomicOr(&c->bad_ts, 1u);
+}
+
 // ---------------------------------------------------------------- up-sweeps and scans
 
 template <typename KT>
@@ -357,7 +426,9 @@ struct ValLoader {
 // Pass 0 of the keyed sort: builds the record from the original columns. Key and compared-attribute column
 // types are template parameters. c1 comes from prep's bit mask, or (c1_inline: c1 reads only the compared
 // attribute) is evaluated here on the loaded value.
-template <typename KT, typename VT>
+// TS: the pass also checks that event time does not decrease (pass0_kernel's optional time-order hooks, pass0_dev.h),
+// for batches whose prep read the key column only (prep_keys_kernel): the whole timestamp is loaded, not its low half.
+template <typename KT, typename VT, bool TS = false>
 struct OrigSrc {
   const NfaStream* st;
   const KT* kcol;
@@ -374,20 +445,30 @@ struct OrigSrc {
   int c1len;
   const DVal* consts;
   bool c1_inline;
+  uint32_t* ts_flag;  // TS: raised when event time decreases somewhere in the batch
   Cond c1;
+  static constexpr bool kTimeOrder = TS;
+  // TS is chosen only for batches with no ordinal column and c1 evaluated here (the keys-only prep's case): known at
+  // compile time there, so that instantiation has neither the ordinal and mask loads nor their kernel arguments in
+  // scalar registers
+  __device__ bool has_ord() const { return !TS && ord != nullptr; }
+  __device__ bool inl() const { return TS || c1_inline; }
+  __device__ int64_t time0() const { return ts0; }
+  __device__ int64_t time_at(int64_t p) const { return ts[p]; }
+  __device__ void time_bad() const { atomicOr(ts_flag, 1u); }
   __device__ void init() {
-    if (c1_inline) c1 = make_cond(c1code, c1len, consts);
+    if (inl()) c1 = make_cond(c1code, c1len, consts);
   }
   __device__ uint32_t c1_bit(VT v, uint64_t m, int64_t p) const {
-    if (c1_inline) return eval_simple(c1, ValLoader<VT>{v}) ? 1u : 0u;
+    if (inl()) return eval_simple(c1, ValLoader<VT>{v}) ? 1u : 0u;
     return (uint32_t)(m >> (p & 63)) & 1u;
   }
   __device__ uint4 rec(int64_t p) const {
     uint4 r;
     const VT v = vcol[p];
-    const uint64_t m = c1_inline ? 0ull : c1mask[p >> 6];
+    const uint64_t m = inl() ? 0ull : c1mask[p >> 6];
     r.x = (uint32_t)((int64_t)kcol[p] - kmin) | (c1_bit(v, m, p) << 31);
-    r.y = ord ? (uint32_t)(ord[p] - obase) : (uint32_t)p;
+    r.y = has_ord() ? (uint32_t)(ord[p] - obase) : (uint32_t)p;
     r.z = vcode<VT>(v, vmode, vmin);
     r.w = (uint32_t)(ts[p] - ts0);
     return r;
@@ -399,44 +480,47 @@ struct OrigSrc {
   // the ordinal as loaded: obase is subtracted where it is used, so that load() itself needs no loaded value and a
   // tile's loads all issue before the first wait. o without an ordinal column and m with c1 evaluated inline are
   // left unset and never read: a constant moved into a register that a load of the tile before also wrote would be
-  // a vmcnt wait inside load().
+  // a vmcnt wait inside load(). TS: t is the whole timestamp (its high half only to see that ts - ts0 fits 32 bits).
   struct Raw {
     uint32_t k;
     VT v;
-    uint32_t t, o, m;
+    typename std::conditional<TS, int64_t, uint32_t>::type t;
+    uint32_t o, m;
   };
+  __device__ int64_t time_of(const Raw& r) const { return (int64_t)r.t; }
   __device__ Raw load(int64_t p) const {
     Raw r;
-    const uint32_t* t32 = (const uint32_t*)(ts + p);  // little endian: the low half first
+    typedef typename std::conditional<TS, int64_t, uint32_t>::type TT;
+    const TT* t32 = (const TT*)(ts + p);  // little endian: the low half first
 #if SM_ORIG_NT_LOAD
     // read-once columns: nontemporal loads keep the L2 for the pass's scattered record stores (as RecSrc)
     r.k = __builtin_nontemporal_load((const uint32_t*)(kcol + p));
     r.v = __builtin_nontemporal_load(vcol + p);
     r.t = __builtin_nontemporal_load(t32);
-    if (ord) r.o = __builtin_nontemporal_load((const uint32_t*)(ord + p));
+    if (has_ord()) r.o = __builtin_nontemporal_load((const uint32_t*)(ord + p));
 #else
     r.k = *(const uint32_t*)(kcol + p);
     r.v = vcol[p];
     r.t = *t32;
-    if (ord) r.o = *(const uint32_t*)(ord + p);
+    if (has_ord()) r.o = *(const uint32_t*)(ord + p);
 #endif
-    if (!c1_inline) r.m = ((const uint32_t*)c1mask)[p >> 5];
+    if (!inl()) r.m = ((const uint32_t*)c1mask)[p >> 5];
     return r;
   }
-  __device__ uint32_t rel_ord(const Raw& r, int64_t p) const { return ord ? r.o - (uint32_t)obase : (uint32_t)p; }
+  __device__ uint32_t rel_ord(const Raw& r, int64_t p) const { return has_ord() ? r.o - (uint32_t)obase : (uint32_t)p; }
   __device__ uint32_t c1_of(const Raw& r, int64_t p) const {
-    if (c1_inline) return eval_simple(c1, ValLoader<VT>{r.v}) ? 1u : 0u;
+    if (inl()) return eval_simple(c1, ValLoader<VT>{r.v}) ? 1u : 0u;
     return (r.m >> (p & 31)) & 1u;
   }
   __device__ void split(const Raw& r, int64_t p, uint64_t& a, uint64_t& b) const {
     const uint32_t c1 = c1_of(r, p);
     a = (uint64_t)((r.k - (uint32_t)kmin) | (c1 << 31)) | ((uint64_t)rel_ord(r, p) << 32);
-    b = (uint64_t)vcode<VT>(r.v, vmode, vmin) | ((uint64_t)(r.t - (uint32_t)ts0) << 32);
+    b = (uint64_t)vcode<VT>(r.v, vmode, vmin) | ((uint64_t)((uint32_t)r.t - (uint32_t)ts0) << 32);
   }
   __device__ uint4 record(const Raw& r, int64_t p) const {  // pass0_kernel (pass0_dev.h)
     const uint32_t c1 = c1_of(r, p);
     return make_uint4((r.k - (uint32_t)kmin) | (c1 << 31), rel_ord(r, p), vcode<VT>(r.v, vmode, vmin),
-                      r.t - (uint32_t)ts0);
+                      (uint32_t)r.t - (uint32_t)ts0);
   }
   __device__ void flush() {}
 };
@@ -1548,14 +1632,33 @@ bool c1_inline(const FastHostInfo& hi, const FastArgs& a) {
   return true;
 }
 
+// key pass 0 is pass0_kernel (pass0_dev.h; A/B: SM_PASS0_V2=0 runs the generic write-combining down-sweep)
+bool pass0_v2() {
+  static const bool on = !(getenv("SM_PASS0_V2") && getenv("SM_PASS0_V2")[0] == '0');
+  return sort_wc() && on;
+}
+
+// ts_flag: the batch took the keys-only prep, and pass 0 (pass0_kernel only) raises *ts_flag when event time decreases
 template <typename KT, typename VT>
 void launch_down0_t(const FastHostInfo& hi, const FastArgs& a, const void* kcol, int64_t kmin, int vmode, int64_t vmin,
                     const uint64_t* c1mask, int64_t ts0, int G, int64_t per, hipStream_t s, uint4* dst,
-                    const uint32_t* cnt, const uint32_t* dbase) {
+                    const uint32_t* cnt, const uint32_t* dbase, uint32_t* ts_flag) {
+  if (ts_flag) {  // (never with a LONG compared attribute, which keeps the full prep: no such instantiation)
+    if constexpr (std::is_same<VT, int64_t>::value) {
+      throw std::logic_error("the time-order check of pass 0 is not built for a LONG compared attribute");
+    } else {
+      if (!pass0_v2() || a.ordinals || !c1_inline(hi, a))
+        throw std::logic_error("the time-order check of pass 0: pass0_kernel, no ordinal column, c1 inline");
+      OrigSrc<KT, VT, true> os{a.st, (const KT*)kcol, (const VT*)hi.cols[hi.vattr], kmin, vmode, vmin, c1mask, a.ts,
+                               ts0, a.ordinals, a.ordinal_base, a.code + a.c1_off, a.c1_len, a.consts, true, ts_flag};
+      hipLaunchKernelGGL((pass0_kernel<OrigSrc<KT, VT, true>>), dim3(G), dim3(kP0Block), 0, s, os, dst, a.n, per, G,
+                         cnt, dbase);
+    }
+    return;
+  }
   OrigSrc<KT, VT> os{a.st, (const KT*)kcol, (const VT*)hi.cols[hi.vattr], kmin, vmode, vmin, c1mask, a.ts, ts0,
-                     a.ordinals, a.ordinal_base, a.code + a.c1_off, a.c1_len, a.consts, c1_inline(hi, a)};
-  static const bool p0v2 = !(getenv("SM_PASS0_V2") && getenv("SM_PASS0_V2")[0] == '0');
-  if (sort_wc() && p0v2)  // pass0_dev.h (A/B: SM_PASS0_V2=0 runs the generic write-combining down-sweep)
+                     a.ordinals, a.ordinal_base, a.code + a.c1_off, a.c1_len, a.consts, c1_inline(hi, a), nullptr};
+  if (pass0_v2())
     hipLaunchKernelGGL((pass0_kernel<OrigSrc<KT, VT>>), dim3(G), dim3(kP0Block), 0, s, os, dst, a.n, per, G, cnt, dbase);
   else if (sort_wc())
     hipLaunchKernelGGL((downsweep_wc_kernel<0, OrigSrc<KT, VT>>), dim3(G), dim3(kWcBlock), 0, s, os, dst, nullptr, a.n,
@@ -1568,12 +1671,16 @@ void launch_down0_t(const FastHostInfo& hi, const FastArgs& a, const void* kcol,
 template <typename KT>
 void launch_down0_k(const FastHostInfo& hi, const FastArgs& a, const void* kcol, int64_t kmin, int vmode, int64_t vmin,
                     const uint64_t* m, int64_t ts0, int G, int64_t per, hipStream_t s, uint4* dst,
-                    const uint32_t* cnt, const uint32_t* dbase) {
+                    const uint32_t* cnt, const uint32_t* dbase, uint32_t* tf) {
   switch (hi.vtype) {
-    case T_INT: launch_down0_t<KT, int32_t>(hi, a, kcol, kmin, vmode, vmin, m, ts0, G, per, s, dst, cnt, dbase); break;
-    case T_LONG: launch_down0_t<KT, int64_t>(hi, a, kcol, kmin, vmode, vmin, m, ts0, G, per, s, dst, cnt, dbase); break;
-    case T_FLOAT: launch_down0_t<KT, float>(hi, a, kcol, kmin, vmode, vmin, m, ts0, G, per, s, dst, cnt, dbase); break;
-    case T_DOUBLE: launch_down0_t<KT, double>(hi, a, kcol, kmin, vmode, vmin, m, ts0, G, per, s, dst, cnt, dbase); break;
+    case T_INT: launch_down0_t<KT, int32_t>(hi, a, kcol, kmin, vmode, vmin, m, ts0, G, per, s, dst, cnt, dbase, tf);
+      break;
+    case T_LONG: launch_down0_t<KT, int64_t>(hi, a, kcol, kmin, vmode, vmin, m, ts0, G, per, s, dst, cnt, dbase, tf);
+      break;
+    case T_FLOAT: launch_down0_t<KT, float>(hi, a, kcol, kmin, vmode, vmin, m, ts0, G, per, s, dst, cnt, dbase, tf);
+      break;
+    case T_DOUBLE: launch_down0_t<KT, double>(hi, a, kcol, kmin, vmode, vmin, m, ts0, G, per, s, dst, cnt, dbase, tf);
+      break;
     default: throw std::runtime_error("fast path: unsupported compared-attribute type");
   }
 }
@@ -1835,6 +1942,9 @@ int64_t fast_every_within_v2(const FastArgs& a, const FastHostInfo& hi, FastStat
 
   // column facts + c1 mask + pass-0 digit counts, one pass
   const bool mask = !keyed || !c1_inline(hi, a);
+  // keys-only prep (prep_keys_kernel): the time-order check moves into key pass 0, which raises *ts_flag; only with
+  // pass0_kernel (the A/B down-sweeps keep the full prep)
+  const bool late_ts = keyed && !mask && !a.ordinals && !vlong && pass0_v2();
 #define SM_PREP2(KT, M, X)                                                                                          \
   hipLaunchKernelGGL((prep_kernel<KT, M, X>), dim3(G), dim3(kBlock), 0, s, (const KT*)kcol, vlong, a.ts, a.ordinals, \
                      a.ordinal_base, n, per, G, a.st, a.code + a.c1_off, a.c1_len, a.consts, c1mask, cnt, c)
@@ -1845,7 +1955,14 @@ int64_t fast_every_within_v2(const FastArgs& a, const FastHostInfo& hi, FastStat
     else                                \
       SM_PREP2(KT, M, false);           \
   } while (0)
-  if (key_type == T_LONG && keyed) {
+  if (late_ts) {
+    if (key_type == T_LONG)
+      hipLaunchKernelGGL((prep_keys_kernel<int64_t>), dim3(G), dim3(kBlock), 0, s, (const int64_t*)kcol, a.ts, n, per, G,
+                         cnt, c);
+    else
+      hipLaunchKernelGGL((prep_keys_kernel<int32_t>), dim3(G), dim3(kBlock), 0, s, (const int32_t*)kcol, a.ts, n, per, G,
+                         cnt, c);
+  } else if (key_type == T_LONG && keyed) {
     if (mask) SM_PREP(int64_t, true);
     else SM_PREP(int64_t, false);
   } else {
@@ -1858,13 +1975,32 @@ int64_t fast_every_within_v2(const FastArgs& a, const FastHostInfo& hi, FastStat
   Ctrl hc;
   SM_HIP(hipMemcpyAsync(&hc, c, sizeof(Ctrl), hipMemcpyDeviceToHost, s));
   SM_HIP(hipStreamSynchronize(s));
+  // A batch of the keys-only prep that leaves before key pass 0 (time span, key span): is its event time in order?
+  // Non-monotone goes first, as when prep answered it: FAST_KEY_SPAN lets the caller change the query's key mapping.
+  // One more read of the time column, on those exits only.
+  auto late_bad_ts = [&]() -> bool {
+    if (!late_ts || a.within < 0) return false;
+    hipLaunchKernelGGL(ts_order_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0, s, a.ts,
+                       n, c);
+    unsigned int bad = 0;
+    SM_HIP(hipMemcpyAsync(&bad, &c->bad_ts, sizeof bad, hipMemcpyDeviceToHost, s));
+    SM_HIP(hipStreamSynchronize(s));
+    return bad != 0;
+  };
   if (a.within >= 0) {
-    // the closed form needs non-decreasing event time, inside the batch and after the carried state
+    // the closed form needs non-decreasing event time, inside the batch (late_ts: key pass 0 answers that, below)
+    // and after the carried state
     if (hc.bad_ts || (carry.active && hc.ts0 < carry.ts_last)) {
       sc.used = mark;
       return FAST_NON_MONOTONE;
     }
-    if ((unsigned long long)(hc.ts_last - hc.ts0) >= 0xffffffffull) return bail();
+    if ((unsigned long long)(hc.ts_last - hc.ts0) >= 0xffffffffull) {
+      if (late_bad_ts()) {
+        sc.used = mark;
+        return FAST_NON_MONOTONE;
+      }
+      return bail();
+    }
   }
   if (hc.omax >= 0x7fffffffull || hc.bad_ord) return bail();
   int kbits = 0;
@@ -1876,8 +2012,9 @@ int64_t fast_every_within_v2(const FastArgs& a, const FastHostInfo& hi, FastStat
     kspan = (uint64_t)((int64_t)(hc.kmax ^ 0x8000000000000000ull) - kmin);
     kbits = std::max(1, bits_for(kspan));
     if (kbits > 30 || (hi.remap_span > 0 && kspan > (uint64_t)hi.remap_span)) {
+      const bool bad = late_bad_ts();
       sc.used = mark;
-      return FAST_KEY_SPAN;
+      return bad ? FAST_NON_MONOTONE : FAST_KEY_SPAN;
     }
   }
   // value code of the compared attribute
@@ -1938,17 +2075,36 @@ int64_t fast_every_within_v2(const FastArgs& a, const FastHostInfo& hi, FastStat
   if (keyed) {
     uint4* A = (uint4*)sc.take(n * 16);
     uint4* B = (uint4*)sc.take(n * 16);
-    // key pass 0 from the original columns (its digit counts came from prep)
-    scan_counts(G);
-    if (key_type == T_INT)
-      launch_down0_k<int32_t>(hi, a, kcol, kmin, vmode, vmin, c1mask, hc.ts0, G, per, s, A, cnt, dbase);
-    else launch_down0_k<int64_t>(hi, a, kcol, kmin, vmode, vmin, c1mask, hc.ts0, G, per, s, A, cnt, dbase);
-    tmark("key_pass0");
     // bucket-stack pipeline when the per-bucket keys fill a workgroup (stack.hip); it falls back here otherwise
     const int H = (int)std::min<uint64_t>(kspan >> kRB, 1ull << 20) + 1;
     const bool order_op = spec >= 0 && (spec >> 1) != CMP_EQ && (spec >> 1) != CMP_NE;
     const bool ts_ok = a.within < 0 || (a.within < (1ll << 30) && hc.ts_last - hc.ts0 < (1ll << 30));
-    if (stack_mode != 2 && order_op && ts_ok && H <= kBins && (stack_mode == 1 || H >= kBins / 2)) {
+    const bool stack = stack_mode != 2 && order_op && ts_ok && H <= kBins && (stack_mode == 1 || H >= kBins / 2);
+    // late_ts: the word key pass 0 raises when event time decreases. On the stack route it is word 3 of the
+    // pipeline's status words, which the pipeline reads back before its stack kernel anyway; on the sort / walk
+    // route word 2 of cflags, read back right after the pass (no later kernel sees a batch out of time order).
+    uint32_t* sstat = nullptr;
+    if (late_ts && stack) {
+      sstat = (uint32_t*)sc.take(16);
+      SM_HIP(hipMemsetAsync(sstat, 0, 16, s));
+    }
+    uint32_t* ts_flag = late_ts ? (stack ? sstat + 3 : cflags + 2) : nullptr;
+    // key pass 0 from the original columns (its digit counts came from prep)
+    scan_counts(G);
+    if (key_type == T_INT)
+      launch_down0_k<int32_t>(hi, a, kcol, kmin, vmode, vmin, c1mask, hc.ts0, G, per, s, A, cnt, dbase, ts_flag);
+    else launch_down0_k<int64_t>(hi, a, kcol, kmin, vmode, vmin, c1mask, hc.ts0, G, per, s, A, cnt, dbase, ts_flag);
+    tmark("key_pass0");
+    if (late_ts && !stack && a.within >= 0) {
+      uint32_t bad = 0;
+      SM_HIP(hipMemcpyAsync(&bad, ts_flag, 4, hipMemcpyDeviceToHost, s));
+      SM_HIP(hipStreamSynchronize(s));
+      if (bad) {
+        sc.used = mark;
+        return FAST_NON_MONOTONE;
+      }
+    }
+    if (stack) {
       StackPlan sp{};
       sp.rec = A;
       sp.dbase = dbase;
@@ -1968,7 +2124,12 @@ int64_t fast_every_within_v2(const FastArgs& a, const FastHostInfo& hi, FastStat
       sp.ts0 = hc.ts0;
       sp.ts_last = hc.ts_last;
       sp.o0 = (int32_t)hc.o0;
+      sp.status = sstat;
       const int64_t m = stack_pipeline(sp, a, hi, fs, carry, pairs_out, pairs_cap, sc, s, tm);
+      if (m == FAST_NON_MONOTONE) {  // key pass 0 found event time decreasing (late_ts); nothing was changed
+        sc.used = mark;
+        return FAST_NON_MONOTONE;
+      }
       if (m >= 0) {
         fs.last_path = 3;
         if (tm) {

@@ -8,7 +8,20 @@
 //     walked the 16 waves per digit with 32 LDS operations;
 //   * the record moves through LDS once (16-byte slots, 64 KB per 4096-record tile) instead of as two 8-byte halves.
 // A header of its own so the kernel also runs under the host wave emulator (tests/native/pass0_emu.cpp).
+//
+// Time-order check (optional, Src::kTimeOrder): the pass also answers "is the 64-bit event time non-decreasing over
+// the whole batch", from the timestamps it loads for the records anyway, so that prep need not read the time column
+// for it. A source that asks for it supplies time_of(raw) (the event's timestamp), time0() (the batch's first),
+// time_at(p) (a global load, used for the one event before the chunk) and time_bad() (raises the device flag).
+// With rel = ts - time0() in 64 bits, an event is out of order when rel >> 32 != 0 (before the batch's first event,
+// or 2^32 or more after it: the caller has checked that the batch's last event is not, so some later event is
+// earlier) or when its low word is below its predecessor's; with every high word zero the low words compare as the
+// times do. The predecessor of an event is lane - 1 of the same wave-item (one DPP move), lane 63 of the wave's item
+// before (v_readlane), the wave before's last event (one LDS word per wave) or the last event of the tile before
+// (two more LDS words, by tile parity; seeded with the event before the chunk).
 #pragma once
+#include <type_traits>
+
 #include "fastpath_dev.h"
 
 namespace sm {
@@ -64,6 +77,22 @@ __device__ __forceinline__ int64_t p0_opaque(int64_t v) {
   return v;
 }
 
+// whether Src asks for the time-order check (a static member kTimeOrder that is true); sources without it build as
+// before
+template <typename S, typename = void>
+struct p0_time_order : std::false_type {};
+template <typename S>
+struct p0_time_order<S, std::void_t<decltype(S::kTimeOrder)>> : std::integral_constant<bool, S::kTimeOrder> {};
+
+// v of lane - 1 of the wave (lane 0: unspecified, replaced by the caller). Every lane of the wave must be active.
+__device__ __forceinline__ uint32_t p0_lane_before(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+#else
+  return __shfl_up(v, 1, 64);
+#endif
+}
+
 // Chunk blockIdx.x = [blockIdx.x * per, + per) of the batch, tile by tile. cnt[d * G + g] = records of digit d in
 // chunks before g (scan_chunks), dbase[d] = records of digits before d: chunk g's first position for digit d is
 // dbase[d] + cnt[d * G + g].
@@ -78,6 +107,12 @@ __global__ void __launch_bounds__(kP0Block) pass0_kernel(Src src, uint4* __restr
   __shared__ uint32_t cst[kBins];  // first position of the digit's incomplete segment: carried = [cst, run)
   __shared__ __attribute__((aligned(16))) uint4 carry[kBins][kP0Seg - 1];
   __shared__ uint32_t lw[kP0Waves];
+  // time-order check: relative time of wave w's last event of the tile in tlast[w] (w < 15); the tile's last event
+  // (wave 15's) in tlast[15 + parity of the tile], so that the next tile's wave 0 still finds it after wave 15 has
+  // written its own; tbad: some event of the chunk is out of order
+  __shared__ uint32_t tlast[kP0Waves + 1];
+  __shared__ uint32_t tbad;
+  constexpr bool kTO = p0_time_order<Src>::value;
 
   const int tid = threadIdx.x, lane = tid & 63, w = wave_index();
   const int64_t lo = (int64_t)blockIdx.x * per;
@@ -94,7 +129,16 @@ __global__ void __launch_bounds__(kP0Block) pass0_kernel(Src src, uint4* __restr
     row[0] = make_uint4(0, 0, 0, 0);
     row[1] = make_uint4(0, 0, 0, 0);
   }
+  if constexpr (kTO) {
+    if (tid == 0) {
+      tbad = 0u;
+      // the first tile's predecessor: the event before the chunk (whether its own high word is zero is its chunk's
+      // business); none before the batch's first event, whose relative time 0 is below no other
+      tlast[kP0Waves] = (lo > 0 && len > 0) ? (uint32_t)(src.time_at(lo - 1) - src.time0()) : 0u;
+    }
+  }
   lds_barrier();
+  int tpar = 0;  // parity of the tile in the chunk
   typename Src::Raw raw[kP0Items];
   auto load_tile = [&](int64_t base) {
     const int64_t rem = lo + len - base;
@@ -133,11 +177,38 @@ __global__ void __launch_bounds__(kP0Block) pass0_kernel(Src src, uint4* __restr
 #if defined(__HIP_DEVICE_COMPILE__)
     __builtin_amdgcn_s_waitcnt(0x0F70);
 #endif
+    uint32_t tfirst = 0;  // relative time of the wave's first event of the tile (compared after the next barrier)
     if (more) {
+      uint32_t tq[kP0Items];
+      bool tb = false;
 #pragma unroll
       for (int k = 0; k < kP0Items; ++k) {
         const int e = w * 64 * kP0Items + k * 64 + lane;
-        if (e < tile_n) rec[k] = src.record(raw[k], base + e);
+        if constexpr (kTO) tq[k] = 0u;
+        if (e < tile_n) {
+          rec[k] = src.record(raw[k], base + e);
+          if constexpr (kTO) {
+            const int64_t rel = src.time_of(raw[k]) - src.time0();
+            tq[k] = (uint32_t)rel;
+            tb |= ((uint64_t)rel >> 32) != 0;
+          }
+        }
+      }
+      if constexpr (kTO) {
+#pragma unroll
+        for (int k = 0; k < kP0Items; ++k) {
+          const int e = w * 64 * kP0Items + k * 64 + lane;
+          uint32_t pv = p0_lane_before(tq[k]);
+          // lane 0: lane 63 of the item before (all of it is in the tile when this event is); item 0 waits for the
+          // wave before's last event
+          const uint32_t pl = wave_read_lane(tq[k > 0 ? k - 1 : 0], 63);
+          if (lane == 0) pv = k > 0 ? pl : tq[0];
+          tb |= e < tile_n && tq[k] < pv;
+        }
+        // (a wave the tile ends in writes a word no wave reads: the waves after it have no event)
+        if (lane == 63) tlast[w < kP0Waves - 1 ? w : kP0Waves - 1 + tpar] = tq[kP0Items - 1];
+        if (tb) tbad = 1u;
+        tfirst = tq[0];
       }
     }
     p0_store_fence(rec);
@@ -195,6 +266,13 @@ __global__ void __launch_bounds__(kP0Block) pass0_kernel(Src src, uint4* __restr
     // the next tile's loads: no global store between here and their wait at the top of the next iteration
     if (!last) load_tile(base + kP0Tile);
     lds_barrier();
+    if constexpr (kTO) {
+      // the wave's first event against the wave before's last, or the last event of the tile before (written one
+      // tile ago; overwritten two barriers from here at the earliest)
+      if (lane == 0 && w * 64 * kP0Items < tile_n && tfirst < tlast[w > 0 ? w - 1 : kP0Waves - 1 + (tpar ^ 1)])
+        tbad = 1u;
+      tpar ^= 1;
+    }
 
     // digit tid: its tile count and the tile's digit starts (block scan)
     uint32_t ct = 0;
@@ -234,6 +312,10 @@ __global__ void __launch_bounds__(kP0Block) pass0_kernel(Src src, uint4* __restr
     plast = last;
   }
   src.flush();
+  if constexpr (kTO) {
+    // every write of tbad lies before the last tile's placement barriers
+    if (tid == 0 && tbad != 0u) src.time_bad();
+  }
 }
 
 }  // namespace

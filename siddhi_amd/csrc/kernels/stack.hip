@@ -828,10 +828,10 @@ int64_t stack_pipeline(const StackPlan& p, const FastArgs& a, const FastHostInfo
     if (tm) tm->mark(l, s);
   };
   const int64_t n = p.n;
-  uint32_t* err = (uint32_t*)sc.take(16);
+  uint32_t* err = p.status ? p.status : (uint32_t*)sc.take(16);
   uint32_t* cand_n = err + 1;
   uint32_t* stot = err + 2;
-  SM_HIP(hipMemsetAsync(err, 0, 16, s));
+  if (!p.status) SM_HIP(hipMemsetAsync(err, 0, 16, s));  // (else zeroed before key pass 0, which may have set word 3)
   StackArgs sa{};
   sa.rec = (const uint4*)p.rec;
   sa.dbase = p.dbase;
@@ -886,9 +886,13 @@ int64_t stack_pipeline(const StackPlan& p, const FastArgs& a, const FastHostInfo
   }
   uint32_t* sbase = (uint32_t*)sc.take(kBins * 4);
   hipLaunchKernelGGL(stage_base_kernel, dim3(1), dim3(kOB), 0, s, p.dbase, ccnt, sbase, stot);
-  uint32_t hs[3];
-  SM_HIP(hipMemcpyAsync(hs, err, 12, hipMemcpyDeviceToHost, s));
+  uint32_t hs[4];
+  SM_HIP(hipMemcpyAsync(hs, err, 16, hipMemcpyDeviceToHost, s));
   SM_HIP(hipStreamSynchronize(s));
+  if (p.status && p.within >= 0 && hs[3]) {  // key pass 0: event time decreases inside the batch
+    sc.used = mark;
+    return FAST_NON_MONOTONE;
+  }
   if (hs[0] & SE_ORD) {
     sc.used = mark;
     throw std::runtime_error("a carried partial lies more than 2^31 events before the batch's ordinal base (match "
