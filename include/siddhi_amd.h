@@ -126,8 +126,9 @@ int sm_input_send(sm_input* in, int64_t timestamp, const sm_value* row, size_t n
  * carried partials shared with device batches), uploaded in chunks of option "bulk_chunk" events (default 2^24) with
  * the upload of the next chunk overlapping the processing of the current one, and its outputs reach the callbacks
  * chunk by chunk before the call returns. Staged events of such an app take the same pipelines at flush. Such a batch
- * also goes to the device directly when some queries are `every e1=S[c1], e2=S[c2] [within T]` sequences (the
- * adjacent-pair closed form, sm_app_process_device_batch); staged events of an app with such a sequence run on the
+ * also goes to the device directly when some queries are `every e1=S[c1], e2=S[c2] [, ... ek=S[ck]]` sequences of up
+ * to 8 elements on one stream (the adjacent-pair and adjacent-run closed forms, sm_app_process_device_batch); staged
+ * events of an app with such a sequence run on the
  * general NFA kernel, which then keeps the sequence's matching state ("nfa_state:<query>" = 1, "fast_path" 5). */
 int sm_input_send_columns(sm_input* in, size_t n, const int64_t* timestamps, const void* const* cols,
                           const uint8_t* const* null_flags);
@@ -182,7 +183,11 @@ int sm_app_set_option(sm_app* app, const char* key, int64_t value);
  * time going back, a condition outside its envelope) hands the query to the general NFA kernel for good. The
  * sequence is the set of adjacent pairs of each partition instance (a partial is completed or dropped by the
  * instance's next event): it carries at most one event per key, and event time may go back unless it has a `within`;
- * partition keys are a single INT / LONG attribute, other key forms take the NFA kernel. The match
+ * partition keys are a single INT / LONG attribute, other key forms take the NFA kernel. The k-state sequence
+ * `every e1=S[c1], e2=S[c2], ..., ek=S[ck]` (3 <= k <= 8, every element a plain element of this stream, `within` on
+ * elements 2 .. k only, each measured against the previous element's event, no having) is the set of runs of k
+ * adjacent events of each partition instance: it carries the last k - 1 events per key, under the same key and
+ * event-time rules. The match
  * tuples stay on the device (sm_app_device_matches); when a StreamCallback / QueryCallback is registered for a query
  * (or the collect dump is on), its outputs are also projected on the device and delivered as Events before the
  * call returns, in reference order, one callback call per input event that produced output
@@ -277,10 +282,12 @@ int sm_app_copy_device_outputs(sm_app* app, const char* query_name, void* d_dst,
  * not alias d_recs. */
 int sm_order_outputs(const void* d_recs, size_t n, size_t stride, void* d_out, void* hip_stream);
 /* Match tuples of the last device batch for a query: n pairs (e1, e2) of ordinals relative to the batch's
- * ordinal_base, uint32[2*n] in device memory, in reference output order (e2 ordinal, then e1 ordinal). */
+ * ordinal_base, uint32[2*n] in device memory, in reference output order (e2 ordinal, then e1 ordinal). A k-state
+ * sequence (3 <= k <= 8) has k words per tuple, (e1, ..., ek), uint32[k*n], in order of ek: the words per tuple are
+ * the stat "match_arity:<query>". Members carried from an earlier batch are negative as int32. */
 int sm_app_device_matches(sm_app* app, const char* query_name, const uint32_t** d_pairs, size_t* n);
-/* The same tuples (or a filter query's kept rows, uint32 each) copied into a caller-owned device buffer of
- * cap_bytes on hip_stream (asynchronous); *n = tuples. Lets a caller hand them to its own collectives. */
+/* The same tuples (match_arity uint32 words each; a filter query's kept rows: one) copied into a caller-owned device
+ * buffer of cap_bytes on hip_stream (asynchronous); *n = tuples. Lets a caller hand them to its own collectives. */
 int sm_app_copy_device_matches(sm_app* app, const char* query_name, void* d_dst, size_t cap_bytes, size_t* n,
                                void* hip_stream);
 /* One value of a device-side output event: INT / LONG / BOOL / STRING (dictionary id) in i, FLOAT / DOUBLE (FLOAT
@@ -305,7 +312,11 @@ int sm_app_device_project(sm_app* app, const char* query_name, sm_dval* d_values
 /* Diagnostics of the last device batch: "fast_path:<query>" = the device path it took: patterns 3 = bucket-stack
  * kernels, 2 = sort / walk kernels, 1 = general closed form (option fast_general), 5 = general NFA kernel (hand-over);
  * `every e1, e2` sequences 6 = adjacent-pair kernels (labels seq_facts, seq_sort, seq_link, seq_keep, seq_count,
- * seq_scan, seq_emit, seq_carry), 5 = general NFA kernel; filter queries 3 = filter interpreter, 4 = typed conjunction. "output_events:<query>" = its output count.
+ * seq_scan, seq_emit, seq_carry), 5 = general NFA kernel; k-state sequences (3 <= k <= 8) 7 = adjacent-run kernels
+ * (labels seqk_facts, seqk_sort, seqk_link, seqk_keep, seqk_count, seqk_scan, seqk_emit, seqk_carry), 5 = general NFA
+ * kernel; filter queries 3 = filter interpreter, 4 = typed conjunction. "output_events:<query>" = its output count.
+ * "match_arity:<query>" = uint32 words per tuple of sm_app_device_matches: k for a k-state sequence of the adjacent-run
+ * form, 2 for every other pattern or sequence, 1 for a filter (its kept row).
  * "kernel_ms:<label>" / "kernel_calls:<label>" and "fast_ms:group" / "fast_ms:walk" / "fast_ms:order" (per-kernel
  * and phase times in ms; need the "fast_timing" option). "nfa_state:<query>" = 1 once a closed-form query's matching
  * state is held by the general NFA kernel for good: host events it could not take on the closed form (a null value,

@@ -212,9 +212,10 @@ class SiddhiAppRuntime:
     def sendDeviceBatch(self, stream_id, ts, cols, ordinals=None, ordinal_base=0, hip_stream=None):
         """Bulk ingest of one stream's columns already in device memory (torch tensors: int64 event times, one
         tensor per attribute at its native width): the device form of a sequence of InputHandler.send(ts, row)
-        calls (InputHandler.java:53 → StreamJunction.sendData :232). Filter queries and `every e1 -> e2 within T`
-        patterns on the stream run on the GPU; their outputs reach the registered callbacks in the reference's
-        order, one call per input event that produced output (sm_app_process_device_batch)."""
+        calls (InputHandler.java:53 → StreamJunction.sendData :232). Filter queries, `every e1 -> e2 within T`
+        patterns and `every e1=S[c1], e2=S[c2] [, ..., ek=S[ck]]` sequences of up to 8 elements on the stream run on
+        the GPU; their outputs reach the registered callbacks in the reference's order, one call per input event
+        that produced output (sm_app_process_device_batch)."""
         import torch
         n = ts.numel()
         for name, t in [("ts", ts), ("ordinals", ordinals)] + [(f"column {k}", c) for k, c in enumerate(cols)]:

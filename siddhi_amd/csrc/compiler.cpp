@@ -752,6 +752,41 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
         cq.fast_c2_len = pres[1].progLen;
       }
     }
+    // ---- the k-state sibling: every e1=S[c1], e2=S[c2], ..., ek=S[ck], 3 <= k <= 8, all on one stream; `within`
+    // only on elements m >= 2, each measured against the previous element's event (kernels/seqk_dev.h)
+    if (q.input == InputKind::SEQUENCE && root_el->kind == StateKind::NEXT && !root_el->has_within && !q.having) {
+      std::vector<const StateElem*> leaves;
+      bool ok = true;
+      std::function<void(const StateElem*, bool)> walk = [&](const StateElem* el, bool first) {
+        if (el->kind == StateKind::NEXT) {
+          if (el->has_within) ok = false;  // a parenthesised sub-chain with its own within
+          walk(el->a.get(), first);
+          walk(el->b.get(), false);
+        } else if (el->kind == StateKind::EVERY && first && leaves.empty() && !el->has_within &&
+                   el->a->kind == StateKind::STREAM && !el->a->has_within) {
+          leaves.push_back(el->a.get());
+        } else if (el->kind == StateKind::STREAM && !leaves.empty()) {
+          leaves.push_back(el);
+        } else {
+          ok = false;
+        }
+      };
+      walk(root_el, true);
+      const int k = (int)leaves.size();
+      ok = ok && k >= 3 && k <= 8 && h.nslots == k && (int)pres.size() == k;
+      for (int m = 0; ok && m < k; ++m)
+        ok = leaves[m]->stream_id == leaves[0]->stream_id && pres[m].kind == PK_STREAM && pres[m].stateId == m;
+      for (size_t r = 0; ok && r < refs.size(); r += 2)
+        if (!(refs[r + 1] == 0 || refs[r + 1] == kCurrent)) ok = false;
+      if (ok) {
+        cq.fast_seq_k = k;
+        for (int m = 0; m < k; ++m) {
+          cq.fast_k_off[m] = pres[m].progOff;
+          cq.fast_k_len[m] = pres[m].progLen;
+          cq.fast_k_within[m] = m > 0 && leaves[m]->has_within ? leaves[m]->within_ms : -1;
+        }
+      }
+    }
   }
   h.npre = (int)pres.size();
   h.npost = (int)posts.size();
@@ -763,6 +798,7 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
   if (cq.fast_every_within || cq.fast_seq_adjacent) {  // hidden (e1, e2) ordinals for the NFA fallback of device batches
     refs.insert(refs.end(), {0, 0, 1, 0});
   }
+  for (int m = 0; m < cq.fast_seq_k; ++m) refs.insert(refs.end(), {m, 0});  // hidden (e1, ..., ek) ordinals, likewise
   h.nrefs = (int)refs.size() / 2;
   h.nconst = (int)consts.size();
   // per-key state layout (int64 words)

@@ -43,6 +43,15 @@ struct CompiledQuery {
   // fast path: every e1=S[c1], e2=S[c2] [within T] (sequence: adjacent pairs of a partition instance, seqpath.hip);
   // shares fast_within / fast_c1_* / fast_c2_*
   bool fast_seq_adjacent = false;
+  // fast path: every e1=S[c1], e2=S[c2], ..., ek=S[ck] with 3 <= k <= 8 (sequence: runs of k adjacent events of a
+  // partition instance, seqkpath.hip). fast_seq_k = k (0: not this form); per element m (0-based) its condition
+  // program (state context, slots 0..m) and its `within` against the previous element's event (-1 = none; element 0
+  // has none). The plan carries k hidden ordinal refs (slot m, index 0) after the visible ones.
+  int fast_seq_k = 0;
+  int fast_k_off[8] = {0}, fast_k_len[8] = {0};
+  int64_t fast_k_within[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+  // uint32 words per device match tuple: k, 2 for every other state query, 1 for a filter (its kept row)
+  int match_arity() const { return hdr.kind == 0 ? 1 : fast_seq_k ? fast_seq_k : 2; }
 };
 
 struct CompiledPartition {

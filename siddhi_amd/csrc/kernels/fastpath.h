@@ -107,6 +107,21 @@ int64_t fast_every_within_v2(const FastArgs& a, const FastHostInfo& hi, FastStat
 int64_t fast_seq_adjacent(const FastArgs& a, const FastHostInfo& hi, FastState& fs, FastCarry& carry,
                           uint32_t* pairs_out, int64_t pairs_cap, Scratch& sc, hipStream_t s, FastTimings* tm = nullptr);
 
+// The k-state sibling `every e1=S[c1], ..., ek=S[ck]`, 3 <= k <= 8 (seqpath.hip, seq_dev.h: the adjacent-run closed
+// form). a.c1_* / a.c2_* / a.within are not read: the plan's programs and withins come in `p`.
+struct SeqKPlan {
+  int k = 0;
+  int off[8] = {0}, len[8] = {0};  // condition program of element m (state context)
+  int64_t within[8] = {-1, -1, -1, -1, -1, -1, -1, -1};  // element m against element m - 1; -1 = none
+};
+
+// Outputs are k-tuples (k uint32 words each, relative to a.ordinal_base; members carried from earlier batches are
+// negative as int32), at most one per event, in order of the last event. The carry holds each instance's last
+// min(k - 1, events so far) events, sorted by (key, ordinal). Results as fast_seq_adjacent; FAST_NON_MONOTONE only when
+// some element has a within. tuples_cap counts tuples. Sets fs.last_path = 7.
+int64_t fast_seq_k(const FastArgs& a, const SeqKPlan& p, const FastHostInfo& hi, FastState& fs, FastCarry& carry,
+                   uint32_t* tuples_out, int64_t tuples_cap, Scratch& sc, hipStream_t s, FastTimings* tm = nullptr);
+
 // ---- internal: the bucket-stack pipeline (stack.hip), entered by fast_every_within_v2 after key pass 0 ----
 
 // Facts about a batch once key pass 0 has scattered its 16-byte records {key - kmin | c1 << 31, ordinal - base,
@@ -153,7 +168,8 @@ void pair_project(const uint32_t* pairs, int64_t m, const NfaStream* st_dev, con
                   int64_t base, const int64_t* ts, const int64_t* prev_carry, int64_t nc, int cw, const char* blob_dev,
                   DVal* out, int64_t* ts_out, Scratch& sc, hipStream_t s, bool rows = false,
                   int64_t* words = nullptr, uint8_t* nulls = nullptr,  // words / nulls: compact form (nsel <= 8)
-                  const uint32_t* carry_keys = nullptr, const uint32_t* carry_idx = nullptr, bool sync = true);
+                  const uint32_t* carry_keys = nullptr, const uint32_t* carry_idx = nullptr, bool sync = true,
+                  int arity = 2);  // arity k > 2: `pairs` are k-tuples (the adjacent-run closed form), slot s = word s
 // The carried partials' e1 ordinals sorted for pair_project (carry_keys / carry_idx, nc each, in sc): a caller
 // projecting one batch's outputs in several launches sorts them once (round 5: device_outputs' segments)
 void pair_project_carry_order(const int64_t* prev_carry, int64_t nc, int cw, int64_t base, Scratch& sc, hipStream_t s,

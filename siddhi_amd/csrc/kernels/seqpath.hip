@@ -92,6 +92,36 @@ int bits_of(uint64_t x) {
   return b;
 }
 
+// rows in (key, arrival) order: a stable LSD sort of (key - kmin, row) over the key's significant bits
+void seq_sort_rows(const void* kcol, bool key64, int64_t n, int64_t kmin, int kbits, Scratch& sc, hipStream_t s,
+                   const uint32_t** perm, const void** skey) {
+  const bool wide = kbits > 32;
+  uint32_t* si = (uint32_t*)sc.take((size_t)n * 4);
+  uint32_t* si2 = (uint32_t*)sc.take((size_t)n * 4);
+  const dim3 g = seq_grid(n, 256);
+  if (wide) {
+    uint64_t* sk = (uint64_t*)sc.take((size_t)n * 8);
+    uint64_t* sk2 = (uint64_t*)sc.take((size_t)n * 8);
+    hipLaunchKernelGGL((seq_sort_keys_kernel<int64_t, uint64_t>), g, dim3(256), 0, s, (const int64_t*)kcol, n, kmin,
+                       sk, si);
+    const bool alt = radix_sort_pairs<uint64_t>(sk, sk2, si, si2, (size_t)n, 0, kbits, sc, s);
+    *skey = alt ? sk2 : sk;
+    *perm = alt ? si2 : si;
+  } else {
+    uint32_t* sk = (uint32_t*)sc.take((size_t)n * 4);
+    uint32_t* sk2 = (uint32_t*)sc.take((size_t)n * 4);
+    if (key64)
+      hipLaunchKernelGGL((seq_sort_keys_kernel<int64_t, uint32_t>), g, dim3(256), 0, s, (const int64_t*)kcol, n, kmin,
+                         sk, si);
+    else
+      hipLaunchKernelGGL((seq_sort_keys_kernel<int32_t, uint32_t>), g, dim3(256), 0, s, (const int32_t*)kcol, n, kmin,
+                         sk, si);
+    const bool alt = radix_sort_pairs<uint32_t>(sk, sk2, si, si2, (size_t)n, 0, kbits, sc, s);
+    *skey = alt ? sk2 : sk;
+    *perm = alt ? si2 : si;
+  }
+}
+
 }  // namespace
 
 int64_t fast_seq_adjacent(const FastArgs& a, const FastHostInfo& hi, FastState& fs, FastCarry& carry,
@@ -175,30 +205,7 @@ int64_t fast_seq_adjacent(const FastArgs& a, const FastHostInfo& hi, FastState& 
   const void* skey = nullptr;
   const bool wide = kbits > 32;
   if (keyed) {
-    uint32_t* si = (uint32_t*)sc.take((size_t)n * 4);
-    uint32_t* si2 = (uint32_t*)sc.take((size_t)n * 4);
-    const dim3 g = seq_grid(n, 256);
-    if (wide) {
-      uint64_t* sk = (uint64_t*)sc.take((size_t)n * 8);
-      uint64_t* sk2 = (uint64_t*)sc.take((size_t)n * 8);
-      hipLaunchKernelGGL((seq_sort_keys_kernel<int64_t, uint64_t>), g, dim3(256), 0, s, (const int64_t*)kcol, n, kmin,
-                         sk, si);
-      const bool alt = radix_sort_pairs<uint64_t>(sk, sk2, si, si2, (size_t)n, 0, kbits, sc, s);
-      skey = alt ? sk2 : sk;
-      perm = alt ? si2 : si;
-    } else {
-      uint32_t* sk = (uint32_t*)sc.take((size_t)n * 4);
-      uint32_t* sk2 = (uint32_t*)sc.take((size_t)n * 4);
-      if (key64)
-        hipLaunchKernelGGL((seq_sort_keys_kernel<int64_t, uint32_t>), g, dim3(256), 0, s, (const int64_t*)kcol, n, kmin,
-                           sk, si);
-      else
-        hipLaunchKernelGGL((seq_sort_keys_kernel<int32_t, uint32_t>), g, dim3(256), 0, s, (const int32_t*)kcol, n, kmin,
-                           sk, si);
-      const bool alt = radix_sort_pairs<uint32_t>(sk, sk2, si, si2, (size_t)n, 0, kbits, sc, s);
-      skey = alt ? sk2 : sk;
-      perm = alt ? si2 : si;
-    }
+    seq_sort_rows(kcol, key64, n, kmin, kbits, sc, s, &perm, &skey);
     tmark("seq_sort");
   }
   if (tm) SM_HIP(hipEventRecord(tm->ev[1], s));
@@ -268,6 +275,169 @@ int64_t fast_seq_adjacent(const FastArgs& a, const FastHostInfo& hi, FastState& 
   carry.ts_last = carry.active ? std::max<int64_t>(carry.ts_last, h.ts_last) : (int64_t)h.ts_last;
   carry.active = true;
   fs.last_path = 6;
+  if (tm) SM_HIP(hipEventRecord(tm->ev[3], s));
+  sc.used = mark;
+  return m;
+}
+
+// The k-state sibling (seq_dev.h, second half). Per batch: facts and key sort as above, then
+//   seqk_link    predecessor link and hit at every row, carry-out candidates (the last k - 1 rows of every run)
+//   seqk_keep    carried rows that stay
+//   seqk_count / seqk_scan / seqk_emit   k-tuples in row order of the last event
+//   seqk_carry   build_carry over the candidates, sorted by ordinal then key (several rows per key; the candidates'
+//                order, which depends on the order of atomics, is not read)
+int64_t fast_seq_k(const FastArgs& a, const SeqKPlan& p, const FastHostInfo& hi, FastState& fs, FastCarry& carry,
+                   uint32_t* tuples_out, int64_t tuples_cap, Scratch& sc, hipStream_t s, FastTimings* tm) {
+  const int64_t n = a.n;
+  const int k = p.k;
+  if (k < 3 || k > kSeqKMax) return FAST_OUTSIDE;
+  if (n == 0) return 0;
+  if (n >= 0x7fffffffll) return FAST_OUTSIDE;
+  const bool keyed = a.key != nullptr;
+  if (keyed && (hi.key_col < 0 || !(hi.key_type == T_INT || hi.key_type == T_LONG))) return FAST_OUTSIDE;
+  const size_t mark = sc.used;
+  if (tm) {
+    SM_HIP(hipEventRecord(tm->ev[0], s));
+    tm->nmk = 0;
+    tm->mark("start", s);
+  }
+  auto tmark = [&](const char* l) {
+    if (tm) tm->mark(l, s);
+  };
+  const void* kcol = keyed ? (hi.dense_keys ? (const void*)hi.dense_keys : hi.cols[hi.key_col]) : nullptr;
+  const bool key64 = keyed && !hi.dense_keys && hi.key_type == T_LONG;
+  const int nattr = hi.nattr, cw = 3 + nattr;
+  const int64_t nc = carry.n;
+  bool any_within = false;
+  for (int m = 1; m < k; ++m) any_within |= p.within[m] >= 0;
+
+  // ---- facts: nothing is changed before they are read
+  SeqFacts* f = (SeqFacts*)sc.take(sizeof(SeqFacts));
+  {
+    SeqFacts init{};
+    init.kmin = ~0ull;
+    SM_HIP(hipMemcpyAsync(f, &init, sizeof(SeqFacts), hipMemcpyHostToDevice, s));
+  }
+  const dim3 fgrid((unsigned)std::min<int64_t>(2048, (n + kFactsBlock - 1) / kFactsBlock));
+  if (key64)
+    hipLaunchKernelGGL(seq_facts_kernel<int64_t>, fgrid, dim3(kFactsBlock), 0, s, (const int64_t*)kcol, a.ts, a.ordinals,
+                       a.ordinal_base, n, f);
+  else
+    hipLaunchKernelGGL(seq_facts_kernel<int32_t>, fgrid, dim3(kFactsBlock), 0, s, (const int32_t*)kcol, a.ts, a.ordinals,
+                       a.ordinal_base, n, f);
+  if (nc > 0)
+    hipLaunchKernelGGL(seq_carry_check_kernel, seq_grid(nc, 256), dim3(256), 0, s, (const int64_t*)carry.rows, nc,
+                       carry.width, a.ordinal_base, f);
+  tmark("seqk_facts");
+  SeqFacts h;
+  SM_HIP(hipMemcpyAsync(&h, f, sizeof(SeqFacts), hipMemcpyDeviceToHost, s));
+  SM_HIP(hipStreamSynchronize(s));
+  auto leave = [&](int64_t r) {
+    sc.used = mark;
+    return r;
+  };
+  if (any_within && (h.bad_ts || (carry.active && h.ts0 < carry.ts_last))) return leave(FAST_NON_MONOTONE);
+  if (h.bad_ord || h.bad_carry || h.o0 < 0 || h.omax >= 0x7fffffffll) return leave(FAST_OUTSIDE);
+  if (nc > 0 && carry.width != cw) return leave(FAST_OUTSIDE);
+  if (n > tuples_cap) return leave(FAST_OUTSIDE);
+  int64_t kmin = 0, kmax = 0;
+  int kbits = 0;
+  if (keyed) {
+    kmin = (int64_t)(h.kmin ^ 0x8000000000000000ull);
+    kmax = (int64_t)(h.kmax ^ 0x8000000000000000ull);
+    const uint64_t kspan = (uint64_t)(kmax - kmin);
+    kbits = std::max(1, bits_of(kspan));
+    if (!carry.active && hi.remap_span > 0 && (kbits > 30 || kspan > (uint64_t)hi.remap_span))
+      return leave(FAST_KEY_SPAN);
+  }
+
+  // what the carry-out reads lies first, so that the rest is free again when build_carry runs
+  const int64_t cand_cap = n + nc;
+  const int64_t ntiles = (n + kSeqTile - 1) / kSeqTile;
+  {  // scratch for the worst case, before anything changes
+    const uint64_t runs = keyed ? (kbits >= 62 ? (uint64_t)n : std::min<uint64_t>((uint64_t)n, (1ull << kbits))) : 1;
+    const uint64_t ncand_max = std::min<uint64_t>((uint64_t)n, runs * (uint64_t)(k - 1)) + (uint64_t)nc;
+    // sort pairs twice over (+ a histogram word per 4 events), links and hits, tile counts
+    const size_t link = (size_t)n * (keyed ? (kbits > 32 ? 30 : 22) : 5) + (size_t)(ntiles + 2) * 4 + (8 << 20);
+    const size_t build = (size_t)ncand_max * (size_t)(8 * cw + 44) + (8 << 20);
+    if (sc.used + (size_t)cand_cap * 32 + std::max(link, build) + 4096 > sc.cap) return leave(FAST_OUTSIDE);
+  }
+  uint32_t* ctl = (uint32_t*)sc.take(8);  // [0] candidates, [1] tuples
+  int64_t* cand = (int64_t*)sc.take((size_t)cand_cap * 32);
+  const size_t keep = sc.used;
+
+  const uint32_t* perm = nullptr;
+  const void* skey = nullptr;
+  const bool wide = kbits > 32;
+  if (keyed) {
+    seq_sort_rows(kcol, key64, n, kmin, kbits, sc, s, &perm, &skey);
+    tmark("seqk_sort");
+  }
+  if (tm) SM_HIP(hipEventRecord(tm->ev[1], s));
+
+  // ---- link
+  SM_HIP(hipMemsetAsync(ctl, 0, 8, s));
+  SeqKArgs sa{};
+  sa.n = n;
+  sa.ts = a.ts;
+  sa.st = a.st;
+  sa.code = a.code;
+  sa.consts = a.consts;
+  sa.k = k;
+  for (int m = 0; m < kSeqKMax; ++m) {
+    sa.off[m] = m < k ? p.off[m] : 0;
+    sa.len[m] = m < k ? p.len[m] : 0;
+    sa.within[m] = m > 0 && m < k ? p.within[m] : -1;
+  }
+  sa.ordinals = a.ordinals;
+  sa.obase = a.ordinal_base;
+  sa.perm = perm;
+  sa.skey = skey;
+  sa.kmin = kmin;
+  sa.kmax = kmax;
+  sa.carry = (const int64_t*)carry.rows;
+  sa.nc = nc;
+  sa.cw = cw;
+  sa.prev = (int32_t*)sc.take((size_t)n * 4);
+  sa.hit = (uint8_t*)sc.take(((size_t)n + 3) & ~(size_t)3);
+  sa.cand = cand;
+  sa.cand_n = ctl;
+  uint32_t* counts = (uint32_t*)sc.take((size_t)(ntiles + 1) * 4);
+  if (wide) hipLaunchKernelGGL(seqk_link_kernel<uint64_t>, dim3((unsigned)ntiles), dim3(kSeqBlock), 0, s, sa);
+  else hipLaunchKernelGGL(seqk_link_kernel<uint32_t>, dim3((unsigned)ntiles), dim3(kSeqBlock), 0, s, sa);
+  tmark("seqk_link");
+  if (nc > 0) {
+    if (wide) hipLaunchKernelGGL(seqk_keep_kernel<uint64_t>, seq_grid(nc, kSeqBlock), dim3(kSeqBlock), 0, s, sa);
+    else hipLaunchKernelGGL(seqk_keep_kernel<uint32_t>, seq_grid(nc, kSeqBlock), dim3(kSeqBlock), 0, s, sa);
+    tmark("seqk_keep");
+  }
+  if (tm) SM_HIP(hipEventRecord(tm->ev[2], s));
+
+  // ---- tuples in row order
+  hipLaunchKernelGGL(seqk_count_kernel, dim3((unsigned)ntiles), dim3(kSeqBlock), 0, s, (const uint8_t*)sa.hit, n, counts);
+  tmark("seqk_count");
+  exclusive_scan_u32(counts, (size_t)ntiles, sc, s, ctl + 1);
+  tmark("seqk_scan");
+  hipLaunchKernelGGL(seqk_emit_kernel, dim3((unsigned)ntiles), dim3(kSeqBlock), 0, s, (const uint8_t*)sa.hit,
+                     (const int32_t*)sa.prev, n, k, (const uint32_t*)counts, a.ordinals, a.ordinal_base,
+                     (const int64_t*)carry.rows, cw, tuples_out);
+  tmark("seqk_emit");
+  uint32_t hc[2] = {0, 0};
+  SM_HIP(hipMemcpyAsync(hc, ctl, 8, hipMemcpyDeviceToHost, s));
+  SM_HIP(hipStreamSynchronize(s));
+  const int64_t m = hc[1];
+  if (m > tuples_cap || (int64_t)hc[0] > cand_cap) {  // cannot happen (m <= n <= tuples_cap): checked, not assumed
+    sc.used = mark;
+    throw std::runtime_error("adjacent-run closed form: output larger than its buffer");
+  }
+
+  // ---- carry out (build_carry reads the old rows before it replaces them)
+  sc.used = keep;
+  build_carry(sa.cand, (int64_t)hc[0], a.st, nattr, carry, sc, s);
+  tmark("seqk_carry");
+  carry.ts_last = carry.active ? std::max<int64_t>(carry.ts_last, h.ts_last) : (int64_t)h.ts_last;
+  carry.active = true;
+  fs.last_path = 7;
   if (tm) SM_HIP(hipEventRecord(tm->ev[3], s));
   sc.used = mark;
   return m;

@@ -1178,6 +1178,78 @@ __global__ void pair_project_kernel(const uint32_t* __restrict__ pairs, int64_t 
   }
   if (ts_out) ts_out[k] = ts[ld.r2];  // StateEvent.timestamp: the last event's (e2's) event time
 }
+
+// The arity-k sibling (the adjacent-run closed form's k-tuples, 3 <= k <= 8): slot s of output t is the event
+// tuples[k t + s]; any member but the last may be a carried row.
+struct TupleLoader {
+  const NfaStream* st;
+  int64_t r[8];        // batch rows
+  const int64_t* c[8]; // carry rows, or nullptr
+  int k;
+  __device__ StackVal var(const Instr& in) const {
+    if (in.op == OP_COL) return col_value(st, in.a, r[k - 1]);
+    const int s = in.a < 0 ? 0 : in.a >= k ? k - 1 : in.a;
+    if (c[s]) {
+      StackVal v = uncanon((uint64_t)c[s][3 + in.c], in.t0);
+      if (in.t0 == T_STRING) v.null = v.i < 0;
+      return v;
+    }
+    return col_value(st, in.c, r[s]);
+  }
+};
+
+__global__ void tuple_project_kernel(const uint32_t* __restrict__ tuples, int64_t m, int arity,
+                                     const NfaStream* __restrict__ st, const int64_t* __restrict__ ord, int64_t n,
+                                     int64_t base, const int64_t* __restrict__ ts, const int64_t* __restrict__ crow,
+                                     int cw, const uint32_t* __restrict__ ckey, const uint32_t* __restrict__ cidx,
+                                     int64_t nc, const char* __restrict__ blob, DVal* __restrict__ out,
+                                     int64_t* __restrict__ ts_out, int64_t* __restrict__ words,
+                                     uint8_t* __restrict__ nulls) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= m) return;
+  const DQuery* q = (const DQuery*)blob;
+  const Instr* code = (const Instr*)(blob + q->off_code);
+  const DVal* consts = (const DVal*)(blob + q->off_const);
+  const int32_t* sel = (const int32_t*)(blob + q->off_sel);
+  TupleLoader ld;
+  ld.st = st;
+  ld.k = arity;
+  for (int s = 0; s < 8; ++s) {
+    ld.r[s] = 0;
+    ld.c[s] = nullptr;
+    if (s >= arity) continue;
+    const uint32_t e = tuples[t * arity + s];
+    if ((int32_t)e < 0 && nc > 0) {  // a carried member: its row in the previous carry, by ordinal
+      const uint32_t want = (uint32_t)((int32_t)e + 0x80000000ll);
+      int64_t lo = 0, hi = nc - 1;
+      while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (ckey[mid] < want) lo = mid + 1;
+        else hi = mid;
+      }
+      ld.c[s] = crow + (int64_t)cidx[lo] * cw;
+    } else {
+      ld.r[s] = batch_row(ord, n, base, e);
+    }
+  }
+  uint32_t nb = 0;
+  for (int a = 0; a < q->nsel; ++a) {
+    const StackVal v = eval_prog(code + sel[3 * a], sel[3 * a + 1], consts, ld);
+    DVal d;
+    if (sel[3 * a + 2] == T_FLOAT || sel[3 * a + 2] == T_DOUBLE) d.d = v.d;
+    else d.i = v.i;
+    if (words) {  // compact form (nsel <= 8)
+      words[t * q->nsel + a] = d.i;
+      nb |= (v.null ? 1u : 0u) << a;
+    } else {
+      d.null = v.null;
+      d.pad = 0;
+      out[t * q->nsel + a] = d;
+    }
+  }
+  if (words) nulls[t] = (uint8_t)nb;
+  if (ts_out) ts_out[t] = ts[ld.r[arity - 1]];  // StateEvent.timestamp: the last event's event time
+}
 }  // namespace
 
 void pair_project_carry_order(const int64_t* prev_carry, int64_t nc, int cw, int64_t base, Scratch& sc, hipStream_t s,
@@ -1198,13 +1270,17 @@ void pair_project_carry_order(const int64_t* prev_carry, int64_t nc, int cw, int
 void pair_project(const uint32_t* pairs, int64_t m, const NfaStream* st_dev, const int64_t* ord, int64_t n,
                   int64_t base, const int64_t* ts, const int64_t* prev_carry, int64_t nc, int cw, const char* blob_dev,
                   DVal* out, int64_t* ts_out, Scratch& sc, hipStream_t s, bool rows, int64_t* words,
-                  uint8_t* nulls, const uint32_t* carry_keys, const uint32_t* carry_idx, bool sync) {
+                  uint8_t* nulls, const uint32_t* carry_keys, const uint32_t* carry_idx, bool sync, int arity) {
   if (m <= 0) return;
   const size_t mark = sc.used;
   const uint32_t *ck = carry_keys, *ci = carry_idx;
   if (nc > 0 && !rows && !ck) pair_project_carry_order(prev_carry, nc, cw, base, sc, s, &ck, &ci);
-  hipLaunchKernelGGL(pair_project_kernel, grid_of(m), dim3(256), 0, s, pairs, m, st_dev, ord, n, base, ts, prev_carry,
-                     cw, ck, ci, nc, blob_dev, rows, out, ts_out, words, nulls);
+  if (arity > 2 && !rows)
+    hipLaunchKernelGGL(tuple_project_kernel, grid_of(m), dim3(256), 0, s, pairs, m, arity, st_dev, ord, n, base, ts,
+                       prev_carry, cw, ck, ci, nc, blob_dev, out, ts_out, words, nulls);
+  else
+    hipLaunchKernelGGL(pair_project_kernel, grid_of(m), dim3(256), 0, s, pairs, m, st_dev, ord, n, base, ts, prev_carry,
+                       cw, ck, ci, nc, blob_dev, rows, out, ts_out, words, nulls);
   SM_HIP(hipGetLastError());
   if (sync) {
     SM_HIP(hipStreamSynchronize(s));

@@ -116,7 +116,8 @@ struct HostOut {
   const int64_t* refs = nullptr;
   int nvals = 0, nrefs = 0;
   int qidx;
-  int64_t e1 = -1, e2 = -1;  // closed-form queries: ordinals of the match's two events (hidden references)
+  int64_t e1 = -1, e2 = -1;  // closed-form queries: ordinals of the match's first and last events (hidden references)
+  const int64_t* tuple = nullptr;  // k-state sequences: the k hidden references (the match's events in slot order)
   int64_t key_code = 0;      // partition queries: the instance's key code (an inner stream's routing key)
 };
 
@@ -130,6 +131,7 @@ struct DevOut {
   const int64_t* hts;
   bool rows;
   int64_t base;
+  int arity = 2;        // uint32 words per tuple of hp (a filter's rows: 1)
   const int64_t* hw = nullptr;  // compact form: one 64-bit word per value ...
   const uint8_t* hn = nullptr;  // ... and one byte of null flags per output (bit a: value a)
   // segments still in flight (round 5): outputs [seg_end[i-1], seg_end[i]) are in host memory once seg_ev[i] has
@@ -365,7 +367,7 @@ struct QueryRt {
   bool nfa_mode = false;     // a closed-form query handed to the NFA kernel for good (nfa_device_batch)
   int level = 0;             // chaining depth: 0 reads input streams only, L reads a stream a level L-1 query fills
   int nfa_kernel_used = 0;   // 1 = query-specialised NFA kernel, 2 = interpreter (last batch this query ran on the NFA)
-  int fast_path_used = 0;    // 6 = adjacent pairs (sequence), 5 = NFA kernel, 3 = bucket stack, 2 = onesweep form,
+  int fast_path_used = 0;    // 7 = adjacent runs (k-state sequence), 6 = adjacent pairs (sequence), 5 = NFA kernel, 3 = bucket stack, 2 = onesweep form,
                              // 1 = general form (last device batch)
   // what sm_app_device_project needs of the last closed-form batch: its stream, event times, ordinals, and the
   // carry as it was before the batch (carried e1 rows)
@@ -441,7 +443,22 @@ bool seq_progs_ok(const CompiledQuery& cq) {
 }
 
 // A query with a closed form over device batches: the pattern `every e1 -> e2 within T` or its sequence sibling.
-inline bool closed_form(const CompiledQuery& cq) { return cq.fast_every_within || cq.fast_seq_adjacent; }
+inline bool closed_form(const CompiledQuery& cq) {
+  return cq.fast_every_within || cq.fast_seq_adjacent || cq.fast_seq_k > 0;
+}
+
+// The adjacent-run kernels (seqpath.hip fast_seq_k) evaluate element m's condition over slots 0 .. m, one event each:
+// no timestamp reads, no stream-context loads, index 0 or CURRENT only.
+bool seqk_progs_ok(const CompiledQuery& cq) {
+  const Instr* code = (const Instr*)(cq.blob.data() + cq.hdr.off_code);
+  for (int m = 0; m < cq.fast_seq_k; ++m)
+    for (int k = 0; k < cq.fast_k_len[m]; ++k) {
+      const Instr& in = code[cq.fast_k_off[m] + k];
+      if (in.op == OP_TS || in.op == OP_COL) return false;
+      if (in.op == OP_VAR && (in.a < 0 || in.a > m || !(in.b == 0 || in.b == -1))) return false;
+    }
+  return true;
+}
 
 }  // namespace
 }  // namespace sm
@@ -1226,7 +1243,11 @@ void read_outputs(sm_app* a, int qidx, const void* dev, int64_t n, std::vector<H
     const int64_t* rf = (const int64_t*)(b + sizeof(OutRec) + cq.hdr.nsel * sizeof(DVal));
     h.refs = rf;
     h.nrefs = cq.hdr.nrefs_vis;
-    if (cq.hdr.nrefs == cq.hdr.nrefs_vis + 2) {
+    if (cq.fast_seq_k) {  // k hidden refs: the match's events in slot order
+      h.tuple = rf + cq.hdr.nrefs_vis;
+      h.e1 = h.tuple[0];
+      h.e2 = h.tuple[cq.fast_seq_k - 1];
+    } else if (cq.fast_every_within || cq.fast_seq_adjacent) {  // two hidden refs: (e1, e2)
       h.e1 = rf[cq.hdr.nrefs_vis];
       h.e2 = rf[cq.hdr.nrefs_vis + 1];
     }
@@ -1617,12 +1638,17 @@ int64_t nfa_device_batch(sm_app* a, int qi, int s, size_t n, const int64_t* d_ts
   std::stable_sort(outs.begin(), outs.end(), [](const HostOut& x, const HostOut& y) {
     return x.r.pos != y.r.pos ? x.r.pos < y.r.pos : x.r.seq < y.r.seq;
   });
-  std::vector<uint32_t> pairs(outs.size() * 2);
+  const size_t ar = (size_t)q.cq.match_arity();  // 2, or k words per tuple for a k-state sequence
+  std::vector<uint32_t> pairs(outs.size() * ar);
   for (size_t k = 0; k < outs.size(); ++k) {
-    if (outs[k].r.pos < nc || outs[k].e1 < 0 || outs[k].e2 < 0)
+    if (outs[k].r.pos < nc || outs[k].e1 < 0 || outs[k].e2 < 0 || (ar > 2 && !outs[k].tuple))
       throw std::runtime_error("query '" + q.cq.name + "': internal error in the hand-over of carried partials");
-    pairs[2 * k] = (uint32_t)(outs[k].e1 - ordinal_base);
-    pairs[2 * k + 1] = (uint32_t)(outs[k].e2 - ordinal_base);
+    if (ar > 2) {
+      for (size_t m = 0; m < ar; ++m) pairs[ar * k + m] = (uint32_t)(outs[k].tuple[m] - ordinal_base);
+    } else {
+      pairs[2 * k] = (uint32_t)(outs[k].e1 - ordinal_base);
+      pairs[2 * k + 1] = (uint32_t)(outs[k].e2 - ordinal_base);
+    }
   }
   q.dev_pairs.ensure(std::max<size_t>(pairs.size() * 4, 16));
   if (!pairs.empty())
@@ -1673,7 +1699,8 @@ void device_outputs(sm_app* a, int qi, hipStream_t hs, std::vector<DevOut>& outs
   const CompiledQuery& cq = q.cq;
   const bool rows = cq.hdr.kind == 0;
   const int ns = cq.hdr.nsel;
-  const size_t np = (size_t)m * (rows ? 1 : 2);
+  const int ar = cq.match_arity();
+  const size_t np = (size_t)m * ar;
   uint32_t* hp = (uint32_t*)a->out_arena.take(np * 4);
   SM_HIP(hipMemcpyAsync(hp, q.dev_pairs.p, np * 4, hipMemcpyDeviceToHost, hs));
   hipEvent_t pairs_ev = nullptr;
@@ -1713,10 +1740,10 @@ void device_outputs(sm_app* a, int qi, hipStream_t hs, std::vector<DevOut>& outs
     int64_t* dw = compact ? (int64_t*)dvals : nullptr;
     uint8_t* dn = compact ? (uint8_t*)(dvals + (size_t)chunk * ns * 8) : nullptr;
     // stream order keeps segment k's copies ahead of segment k + 1's projection into the same device buffers
-    pair_project((const uint32_t*)q.dev_pairs.p + (rows ? k0 : 2 * k0), c, (const NfaStream*)q.proj_desc_dev.p,
+    pair_project((const uint32_t*)q.dev_pairs.p + ar * k0, c, (const NfaStream*)q.proj_desc_dev.p,
                  q.proj_ord, q.proj_n, q.proj_base, q.proj_ts, (const int64_t*)q.prev_carry.p, q.prev_carry_n,
                  q.prev_carry_w, (const char*)q.blob.p, compact ? nullptr : (DVal*)dvals, dts, a->sc, hs, rows, dw, dn,
-                 ck, ci, !defer);
+                 ck, ci, !defer, ar);
     if (compact) {
       SM_HIP(hipMemcpyAsync(hvals + (size_t)k0 * ns * 8, dw, (size_t)c * ns * 8, hipMemcpyDeviceToHost, hs));
       SM_HIP(hipMemcpyAsync(hvals + (size_t)m * ns * 8 + k0, dn, (size_t)c, hipMemcpyDeviceToHost, hs));
@@ -1732,7 +1759,7 @@ void device_outputs(sm_app* a, int qi, hipStream_t hs, std::vector<DevOut>& outs
     }
   }
   if (!defer) SM_HIP(hipStreamSynchronize(hs));
-  DevOut d{qi, m, hp, compact ? nullptr : (const DVal*)hvals, hts, rows, q.proj_base};
+  DevOut d{qi, m, hp, compact ? nullptr : (const DVal*)hvals, hts, rows, q.proj_base, ar};
   if (compact) {
     d.hw = (const int64_t*)hvals;
     d.hn = (const uint8_t*)(hvals + (size_t)m * ns * 8);
@@ -1770,10 +1797,12 @@ void materialize(sm_app* a, const DevOut& d, std::vector<HostOut>& outs) {
   outs.resize(base + (size_t)d.m);
   parallel_for((size_t)d.m, (size_t)1 << 16, [&](size_t lo, size_t hi) {
     for (size_t k = lo; k < hi; ++k) {
-      const int64_t e1 = d.base + (int32_t)d.hp[d.rows ? k : 2 * k];
-      const int64_t e2 = d.base + (int32_t)d.hp[d.rows ? k : 2 * k + 1];
+      const uint32_t* tp = d.hp + (size_t)d.arity * k;  // slot s of the match = word s (a filter: its row)
+      const int64_t e1 = d.base + (int32_t)tp[0];
+      const int64_t e2 = d.base + (int32_t)tp[d.arity - 1];
       int64_t* rf = hrf + k * nr;
-      for (int r = 0; r < nr; ++r) rf[r] = rslots[2 * r] == 0 ? e1 : e2;
+      for (int r = 0; r < nr; ++r)
+        rf[r] = d.arity > 2 ? d.base + (int32_t)tp[rslots[2 * r]] : rslots[2 * r] == 0 ? e1 : e2;
       HostOut& h = outs[base + k];
       memset(&h.r, 0, sizeof(h.r));
       h.r.pos = e2;
@@ -1807,7 +1836,8 @@ void deliver_direct(sm_app* a, const DevOut& d) {
     return;
   }
   const size_t m = (size_t)d.m;
-  auto trig = [&](size_t k) { return d.rows ? d.hp[k] : d.hp[2 * k + 1]; };
+  const size_t ar = (size_t)d.arity;
+  auto trig = [&](size_t k) { return d.hp[ar * k + ar - 1]; };
   // the call's only outputs: the uniform chunk form (Pending::starts); otherwise PreparedChunks after what is there
   const bool uni = pd.chunks.empty() && !pd.uniform && pd.evs.size() == 0;
   if (!uni) pd.expand();
@@ -2450,7 +2480,7 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
     if (qp->cq.hdr.kind != 0 && !closed_form(qp->cq) &&
         std::find(qp->cq.streams.begin(), qp->cq.streams.end(), s) != qp->cq.streams.end())
       throw sql::UnsupportedError("device batches support filter queries, `every e1 -> e2 within T` patterns and "
-                                  "`every e1, e2 [within T]` sequences; query '" + qp->cq.name +
+                                  "`every e1, e2 [, ... e8]` sequences on one stream; query '" + qp->cq.name +
                                   "' takes sm_app_process_device_events or the host API");
   StreamStage& st = a->streams[s];
   NfaStream d;
@@ -2475,7 +2505,7 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
     // sequences (seqpath.hip): sort pairs, links, dense ids (40 B per event), candidates (32 B per event and carried
     // row) and the carry build's rows and sort arrays for up to 2^24 keys with events plus the carried ones (a batch
     // with more distinct keys than fit is refused by the kernels' host entry before anything changes)
-    if (cq.fast_seq_adjacent)
+    if (cq.fast_seq_adjacent || cq.fast_seq_k)
       need = std::max(need, n * 40 + (n + nc) * 32 + (std::min<size_t>(n, (size_t)1 << 24) + nc) * (48 + 8 * wc) +
                                 ((size_t)64 << 20));
   }
@@ -2534,12 +2564,13 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
     fa.within = cq.fast_within;
     fa.ordinals = d_ordinals;
     fa.ordinal_base = ordinal_base;
-    q.dev_pairs.ensure(std::max<size_t>((n + (size_t)q.carry.n) * 8, 16));
+    // (e1, e2) per match; a k-state sequence: k words per match, at most one match per event
+    q.dev_pairs.ensure(std::max<size_t>(cq.fast_seq_k ? n * 4 * (size_t)cq.fast_seq_k : (n + (size_t)q.carry.n) * 8, 16));
     std::vector<int32_t> types(d.types, d.types + d.nattr);
     FastHostInfo hi;
     hi.cols = d_cols;
     hi.types = types.data();
-    hi.vattr = cq.fast_seq_adjacent ? -1 : fast_vattr(cq, types);
+    hi.vattr = cq.fast_seq_adjacent || cq.fast_seq_k ? -1 : fast_vattr(cq, types);
     hi.c2_host = (const Instr*)(cq.blob.data() + cq.hdr.off_code) + cq.fast_c2_off;
     hi.c2_len = cq.fast_c2_len;
     hi.c1_host = (const Instr*)(cq.blob.data() + cq.hdr.off_code) + cq.fast_c1_off;
@@ -2558,7 +2589,7 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
     // partition keys as dense ids (any key domain): decided at the query's first closed-form batch, then kept, since
     // the carried partials hold ids; ValuePartitionExecutor (core/partition/executor/ValuePartitionExecutor.java:34-39)
     // keys by any value, so a sparse 64-bit id must not leave the closed form
-    if (fa.key && hi.key_col >= 0 && (!a->force_general_fast || cq.fast_seq_adjacent) && n > 0) {
+    if (fa.key && hi.key_col >= 0 && (!a->force_general_fast || cq.fast_seq_adjacent || cq.fast_seq_k) && n > 0) {
       if (q.remap == 0 && !q.carry.active) {
         // option "key_remap", or (automatic) ids when the first batch's key span exceeds the bucket-stack window
         // (2^20): the batch runs on the values with remap_span set, and its prep pass reports a wider span
@@ -2579,9 +2610,22 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
       q.prev_carry.ensure(cb);
       SM_HIP(hipMemcpyAsync(q.prev_carry.p, q.carry.rows, cb, hipMemcpyDeviceToDevice, hs));
     }
-    // the closed form of this query: the pattern's pipelines, or the sequence's adjacent-pair kernels (path 6)
-    const bool seq = cq.fast_seq_adjacent;
+    // the closed form of this query: the pattern's pipelines, the sequence's adjacent-pair kernels (path 6) or, for a
+    // k-state sequence, the adjacent-run kernels (path 7)
+    const bool seq = cq.fast_seq_adjacent || cq.fast_seq_k;
     auto closed = [&]() -> int64_t {
+      if (cq.fast_seq_k) {
+        if (!seqk_progs_ok(cq)) return FAST_OUTSIDE;
+        SeqKPlan kp;
+        kp.k = cq.fast_seq_k;
+        for (int m = 0; m < kp.k; ++m) {
+          kp.off[m] = cq.fast_k_off[m];
+          kp.len[m] = cq.fast_k_len[m];
+          kp.within[m] = cq.fast_k_within[m];
+        }
+        return fast_seq_k(fa, kp, hi, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, (int64_t)n, a->sc, hs,
+                          a->fast_timing ? &a->fast_tm : nullptr);
+      }
       if (seq)
         return seq_progs_ok(cq) ? fast_seq_adjacent(fa, hi, q.fast, q.carry, (uint32_t*)q.dev_pairs.p,
                                                     (int64_t)(n + q.carry.n), a->sc, hs,
@@ -3904,6 +3948,14 @@ int sm_app_get_stat(sm_app* a, const char* key, double* out) {
         throw sql::ValidationError("No query with name " + k.substr(pre.size()));
       }
     }
+    if (k.rfind("match_arity:", 0) == 0) {  // uint32 words per tuple of sm_app_device_matches
+      for (auto& q : a->queries)
+        if (q->cq.name == k.substr(12)) {
+          *out = q->cq.match_arity();
+          return;
+        }
+      throw sql::ValidationError("No query with name " + k.substr(12));
+    }
     if (k.rfind("fast_path:", 0) == 0) {
       for (auto& q : a->queries)
         if (q->cq.name == k.substr(10)) {
@@ -3955,7 +4007,7 @@ int sm_app_copy_device_matches(sm_app* a, const char* query_name, void* d_dst, s
   return guarded([&] {
     for (auto& q : a->queries)
       if (q->cq.name == query_name) {
-        const size_t bytes = (size_t)q->dev_n * (q->cq.hdr.kind == 0 ? 4 : 8);
+        const size_t bytes = (size_t)q->dev_n * 4 * (size_t)q->cq.match_arity();
         if (bytes > cap_bytes) throw std::invalid_argument("copy_device_matches: destination too small");
         if (bytes) SM_HIP(hipMemcpyAsync(d_dst, q->dev_pairs.p, bytes, hipMemcpyDeviceToDevice, (hipStream_t)hip_stream));
         *n = (size_t)q->dev_n;
@@ -4000,7 +4052,8 @@ int sm_app_device_project(sm_app* a, const char* query_name, sm_dval* d_values, 
     a->sc.used = 0;
     pair_project((const uint32_t*)q->dev_pairs.p, m, (const NfaStream*)q->proj_desc_dev.p, q->proj_ord, q->proj_n,
                  q->proj_base, q->proj_ts, (const int64_t*)q->prev_carry.p, q->prev_carry_n, q->prev_carry_w,
-                 (const char*)q->blob.p, (DVal*)d_values, d_ts, a->sc, hs, q->cq.hdr.kind == 0);
+                 (const char*)q->blob.p, (DVal*)d_values, d_ts, a->sc, hs, q->cq.hdr.kind == 0, nullptr, nullptr, nullptr,
+                 nullptr, true, q->cq.match_arity());
   });
 }
 

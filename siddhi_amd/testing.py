@@ -149,8 +149,9 @@ class ProductApp:
         return p.value, n.value
 
     def copy_device_matches(self, query, dst):
-        """The last device batch's tuples into the device tensor `dst` (int64 per tuple = (e2 << 32) | e1, or int32
-        kept rows of a filter) on the current stream; returns the tuple count."""
+        """The last device batch's tuples into the device tensor `dst` (int64 per tuple = (e2 << 32) | e1, int32
+        kept rows of a filter, or k int32 words (e1, ..., ek) per tuple of a k-state sequence: stat match_arity) on
+        the current stream; returns the tuple count."""
         import torch
         n = ctypes.c_size_t()
         s = ctypes.c_void_p(torch.cuda.current_stream(dst.device).cuda_stream)
@@ -201,12 +202,14 @@ class ProductApp:
         return vals, nulls, ts[:m]
 
     def device_matches_host(self, query):
-        """Copy the last device batch's match tuples to the host: numpy uint32 array of shape (n, 2) = (e1, e2)."""
+        """Copy the last device batch's match tuples to the host: numpy uint32 array of shape (n, arity), arity =
+        stat match_arity:<query>: (n, 2) = (e1, e2), or (n, k) = (e1, ..., ek) for a k-state sequence."""
         import numpy as np
         p, n = self.device_matches(query)
-        out = np.empty((n, 2), dtype=np.uint32)
+        arity = max(2, int(self.get_stat("match_arity:" + query)))
+        out = np.empty((n, arity), dtype=np.uint32)
         if n:
-            _hip_memcpy_d2h(out.ctypes.data, p, n * 8)
+            _hip_memcpy_d2h(out.ctypes.data, p, n * 4 * arity)
         return out
 
     def device_rows_host(self, query):

@@ -8,6 +8,8 @@ fast_timing. Each step starts from a fresh runtime state (option reset), as benc
     python tools/seq_bench.py --route closed            # the new kernels
     python tools/seq_bench.py --route nfa               # the NFA route (run it with the parent commit's library too)
     python tools/seq_bench.py --precompile              # CPU only: the NFA route's JIT kernels into the code cache
+    python tools/seq_bench.py --query three ...         # the three-state query `every e1, e2, e3 within T` (three rising
+                                                        # ticks) on the same stream: fast_path 7, the adjacent-run kernels
 
 Step time is a host clock around work that ends in a device synchronise; a run without a GPU fails."""
 import argparse
@@ -24,29 +26,37 @@ import bench  # noqa: E402
 SCHEMA = "define stream StockStream (symbol int, price double, volume long, timestamp long); "
 QUERY = ("@info(name='q') from every e1=StockStream[price>20], e2=StockStream[price>e1.price] within 1 sec "
          "select e1.timestamp as i, e2.timestamp as j insert into OutputStream;")
-APPS = {
-    "keyed": SCHEMA + "partition with (symbol of StockStream) begin " + QUERY + " end;",
-    "unkeyed": SCHEMA + QUERY,
-}
+QUERY3 = ("@info(name='q') from every e1=StockStream[price>20], e2=StockStream[price>e1.price], "
+          "e3=StockStream[price>e2.price] within 1 sec "
+          "select e1.timestamp as i, e2.timestamp as j, e3.timestamp as l insert into OutputStream;")
+
+
+def apps(query):
+    q = QUERY3 if query == "three" else QUERY
+    return {"keyed": SCHEMA + "partition with (symbol of StockStream) begin " + q + " end;", "unkeyed": SCHEMA + q}
+
+
+APPS = apps("pair")
 LABELS = ["seq_facts", "seq_sort", "seq_link", "seq_keep", "seq_count", "seq_scan", "seq_emit", "seq_carry"]
+LABELS += ["seqk_" + l[4:] for l in LABELS]
 
 
-def precompile():
+def precompile(query):
     """The NFA route's query-specialised kernels take minutes through hiprtc: compiled here, on a host without a GPU,
     into siddhi_amd/jit_cache (the compact lane-event form a 4-attribute stream takes), one process per plan."""
     import subprocess
-    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--precompile-one", form],
+    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--query", query, "--precompile-one", form],
                               env=dict(os.environ, SM_NFA_JIT_COMPACT="1")) for form in APPS]
     sys.exit(max(p.wait() for p in procs))
 
 
-def precompile_one(form):
+def precompile_one(form, query):
     import torch  # noqa: F401  (first, as in every run: the library then compiles with the hiprtc torch bundles)
     from siddhi_amd import _lib
     log = ctypes.create_string_buffer(8192)
     size = ctypes.c_size_t()
     t = time.time()
-    rc = _lib.lib().sm_nfa_jit_compile(APPS[form].encode(), 0, log, 8192, ctypes.byref(size))
+    rc = _lib.lib().sm_nfa_jit_compile(apps(query)[form].encode(), 0, log, 8192, ctypes.byref(size))
     print(f"{form}: rc {rc}, {size.value} bytes, {time.time() - t:.0f} s {log.value.decode()[:200]}", flush=True)
     sys.exit(rc)
 
@@ -65,13 +75,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--route", choices=["closed", "nfa"], default="closed")
     ap.add_argument("--forms", default="keyed,unkeyed")
+    ap.add_argument("--query", choices=["pair", "three"], default="pair")
     ap.add_argument("--precompile", action="store_true")
     ap.add_argument("--precompile-one")
     a = ap.parse_args()
     if a.precompile_one:
-        precompile_one(a.precompile_one)
+        precompile_one(a.precompile_one, a.query)
     if a.precompile:
-        precompile()
+        precompile(a.query)
     if a.steps < 10:
         print("note: fewer than 10 timed steps", file=sys.stderr)
 
@@ -90,7 +101,7 @@ def main():
     torch.cuda.synchronize()
     for form in a.forms.split(","):
         opts = {"nfa_jit": 1} if a.route == "nfa" else {}
-        app = ProductApp(APPS[form], **opts)
+        app = ProductApp(apps(a.query)[form], **opts)
         app.set_collect(False)
         cols = [sym, price, price, ordinals]  # volume is not read: aliased
 
@@ -120,7 +131,7 @@ def main():
                     if app.get_stat("kernel_calls:" + lab):
                         kern.setdefault(lab, []).append(app.get_stat("kernel_ms:" + lab))
         st = stats(ms)
-        line = {"route": a.route, "form": form, "events": n, "keys": a.keys, "ts_div": a.ts_div, "steps": a.steps,
+        line = {"route": a.route, "query": a.query, "form": form, "events": n, "keys": a.keys, "ts_div": a.ts_div, "steps": a.steps,
                 "warmup": a.warmup, "ms": st, "events_per_s": n / (st["median"] * 1e-3), "outputs": m,
                 "build_id": build_id}
         if a.route == "closed":
