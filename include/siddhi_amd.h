@@ -203,6 +203,18 @@ int sm_app_process_device_batch(sm_app* app, const char* stream_id, size_t n, co
  * run on the GPU (general NFA kernel, playback timers included); outputs go to the callbacks in reference
  * order before the call returns. Ordinals: d_ordinals[i] if given, else ordinal_base + i. d_stream_idx[i] = -1
  * marks a playback heartbeat (sm_app_advance_time at d_timestamps[i]; no event, no ordinal).
+ * A sequence over several of these streams, `every e1=S1[c1], e2=S2[c2], ..., ek=Sk[ck]` (2 <= k <= 8, at least two
+ * distinct streams, every element a plain element, `within` on elements 2 .. k only, each measured against the previous
+ * element's event, no having; partitioned: every read stream keyed by one INT / LONG attribute of its own), runs its
+ * closed form instead when it is the app's only query and "keep_outputs" is off ("fast_path:<query>" = 8): the set of
+ * runs of k adjacent events of each partition instance among the events of the streams the query reads, each on its
+ * element's stream (events of other streams and heartbeats neither break nor extend a run). It carries the last k - 1
+ * such events per key (with their streams) into the next batch, leaves its match tuples on the device
+ * (sm_app_device_matches, "match_arity:<query>" = k words each; sm_app_device_project) and delivers its outputs as
+ * sm_app_process_device_batch does, leaving the playback clock alone. A batch outside the envelope (event time going
+ * back under a `within`, ordinals that do not fit), or host events staged for one of its streams, hand the query to the
+ * NFA kernel for good, its carried events replayed first ("nfa_state:<query>" = 1, "fast_path:<query>" = 5; the tuples
+ * still go to the device). Same-stream sequences and apps of several queries run on the NFA kernel here, as before.
  * "output_events:<query>" (sm_app_get_stat) = output events of the last such batch; "nfa_kernel:<query>" = which NFA
  * kernel ran it (1 = query-specialised, 2 = interpreter, 0 = none yet). */
 int sm_app_process_device_events(sm_app* app, size_t n, const int32_t* d_stream_idx, const int64_t* d_timestamps,

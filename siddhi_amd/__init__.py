@@ -240,6 +240,31 @@ class SiddhiAppRuntime:
                                                 ordinals.data_ptr() if ordinals is not None else None,
                                                 int(ordinal_base), hip_stream))
 
+    def sendDeviceEvents(self, stream_idx, ts, cols, ordinals=None, ordinal_base=0, hip_stream=None):
+        """Bulk ingest of an interleaved batch over streams that share one schema, already in device memory (torch
+        tensors: the int32 stream index of every event in the order the streams are defined, -1 for a heartbeat; int64
+        event times; one tensor per attribute): the device form of a sequence of InputHandler.send calls on several
+        streams. Pattern and sequence queries run on the GPU and their outputs reach the registered callbacks in the
+        reference's order (sm_app_process_device_events)."""
+        import torch
+        n = ts.numel()
+        named = [("stream_idx", stream_idx), ("ts", ts), ("ordinals", ordinals)]
+        for name, t in named + [(f"column {k}", c) for k, c in enumerate(cols)]:
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or not t.is_contiguous() or t.dim() != 1:
+                raise ValueError(f"sendDeviceEvents: {name} must be a contiguous 1-D tensor on the GPU")
+            if t.numel() != n:
+                raise ValueError(f"sendDeviceEvents: {name} holds {t.numel()} values for {n} events")
+        if stream_idx.dtype != torch.int32:
+            raise ValueError("sendDeviceEvents: stream indices are an int32 tensor")
+        if ts.dtype != torch.int64 or (ordinals is not None and ordinals.dtype != torch.int64):
+            raise ValueError("sendDeviceEvents: event times and ordinals are int64 tensors")
+        ptrs = (ctypes.c_void_p * len(cols))(*[c.data_ptr() for c in cols])
+        check(lib().sm_app_process_device_events(self._h, n, stream_idx.data_ptr(), ts.data_ptr(), ptrs,
+                                                 ordinals.data_ptr() if ordinals is not None else None,
+                                                 int(ordinal_base), hip_stream))
+
     def flush(self):
         check(lib().sm_app_flush(self._h))
 

@@ -773,6 +773,7 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
       };
       walk(root_el, true);
       const int k = (int)leaves.size();
+      const bool walked = ok;
       ok = ok && k >= 3 && k <= 8 && h.nslots == k && (int)pres.size() == k;
       for (int m = 0; ok && m < k; ++m)
         ok = leaves[m]->stream_id == leaves[0]->stream_id && pres[m].kind == PK_STREAM && pres[m].stateId == m;
@@ -784,6 +785,46 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
           cq.fast_k_off[m] = pres[m].progOff;
           cq.fast_k_len[m] = pres[m].progLen;
           cq.fast_k_within[m] = m > 0 && leaves[m]->has_within ? leaves[m]->within_ms : -1;
+        }
+      }
+      // ---- the same shape over several streams of one schema, 2 <= k <= 8 (kernels/mseq_dev.h): a mark of its
+      // own, since such a query runs through the interleaved entry point only
+      bool ms = walked && k >= 2 && k <= 8 && h.nslots == k && (int)pres.size() == k;
+      bool distinct = false;
+      for (int m = 0; ms && m < k; ++m) {
+        ms = pres[m].kind == PK_STREAM && pres[m].stateId == m;
+        distinct |= leaves[m]->stream_id != leaves[0]->stream_id;
+      }
+      ms = ms && distinct;
+      for (size_t r = 0; ms && r < refs.size(); r += 2)
+        if (!(refs[r + 1] == 0 || refs[r + 1] == kCurrent)) ms = false;
+      std::vector<int> keycol(app.streams.size(), -1);
+      for (int m = 0; ms && m < k; ++m) {
+        const int si = lw.metas[m].stream;
+        const StreamDef& d0 = app.streams[lw.metas[0].stream];
+        const StreamDef& d = app.streams[si];
+        ms = d.attrs.size() == d0.attrs.size();
+        for (size_t c = 0; ms && c < d.attrs.size(); ++c) ms = d.attrs[c].type == d0.attrs[c].type;
+        if (!ms || partition < 0) continue;
+        // partitioned: every read stream keyed by one INT / LONG attribute of its own
+        ms = false;
+        for (auto& w : app.partitions[partition].with)
+          if (w.stream_id == d.id && w.key->kind == ExprKind::VAR && w.key->stream_ref.empty()) {
+            const int c = d.index_of(w.key->attr);
+            if (c >= 0 && (d.attrs[c].type == AttrType::INT || d.attrs[c].type == AttrType::LONG)) {
+              keycol[si] = c;
+              ms = true;
+            }
+          }
+      }
+      if (ms) {
+        cq.fast_seq_ms = k;
+        cq.fast_ms_keycol = keycol;
+        for (int m = 0; m < k; ++m) {
+          cq.fast_ms_stream[m] = lw.metas[m].stream;
+          cq.fast_ms_off[m] = pres[m].progOff;
+          cq.fast_ms_len[m] = pres[m].progLen;
+          cq.fast_ms_within[m] = m > 0 && leaves[m]->has_within ? leaves[m]->within_ms : -1;
         }
       }
     }
@@ -799,6 +840,7 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
     refs.insert(refs.end(), {0, 0, 1, 0});
   }
   for (int m = 0; m < cq.fast_seq_k; ++m) refs.insert(refs.end(), {m, 0});  // hidden (e1, ..., ek) ordinals, likewise
+  for (int m = 0; m < cq.fast_seq_ms; ++m) refs.insert(refs.end(), {m, 0});
   h.nrefs = (int)refs.size() / 2;
   h.nconst = (int)consts.size();
   // per-key state layout (int64 words)

@@ -50,8 +50,20 @@ struct CompiledQuery {
   int fast_seq_k = 0;
   int fast_k_off[8] = {0}, fast_k_len[8] = {0};
   int64_t fast_k_within[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+  // fast path: every e1=S1[c1], e2=S2[c2], ..., ek=Sk[ck] with 2 <= k <= 8 over at least two streams of one schema
+  // (sequence: runs of k adjacent events of a partition instance among the events of the streams the query reads,
+  // mseqpath.hip). fast_seq_ms = k (0: not this form); per element m its app stream index, its condition program
+  // (state context, slots 0..m) and its `within` against the previous element's event (-1 = none; element 0 has
+  // none). fast_ms_keycol[s] is the INT / LONG key attribute of app stream s when the query is partitioned (-1: the
+  // query does not read s). The plan carries k hidden ordinal refs (slot m, index 0) after the visible ones. Such a
+  // plan is not fast_seq_k / fast_seq_adjacent: it runs through sm_app_process_device_events only.
+  int fast_seq_ms = 0;
+  int fast_ms_stream[8] = {0};
+  int fast_ms_off[8] = {0}, fast_ms_len[8] = {0};
+  int64_t fast_ms_within[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+  std::vector<int> fast_ms_keycol;
   // uint32 words per device match tuple: k, 2 for every other state query, 1 for a filter (its kept row)
-  int match_arity() const { return hdr.kind == 0 ? 1 : fast_seq_k ? fast_seq_k : 2; }
+  int match_arity() const { return hdr.kind == 0 ? 1 : fast_seq_k ? fast_seq_k : fast_seq_ms ? fast_seq_ms : 2; }
 };
 
 struct CompiledPartition {

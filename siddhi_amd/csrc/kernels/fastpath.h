@@ -122,6 +122,31 @@ struct SeqKPlan {
 int64_t fast_seq_k(const FastArgs& a, const SeqKPlan& p, const FastHostInfo& hi, FastState& fs, FastCarry& carry,
                    uint32_t* tuples_out, int64_t tuples_cap, Scratch& sc, hipStream_t s, FastTimings* tm = nullptr);
 
+// The same form over several streams of one schema, 2 <= k <= 8, on an interleaved batch (seqpath.hip, mseq_dev.h):
+// `sid` is the stream of every row (device); rows of streams outside p.read and heartbeat rows (-1) are ignored.
+struct MSeqPlan {
+  int k = 0;
+  int stream[8] = {0};             // app stream of element m
+  int off[8] = {0}, len[8] = {0};  // condition program of element m (state context)
+  int64_t within[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+  uint64_t read = 0;               // bit s: the query reads app stream s
+  bool keyed = false;
+  const void* kcol[64] = {nullptr};  // keyed: the device key column of read stream s (INT, or LONG when bit s of wide)
+  uint64_t wide = 0;
+  int64_t remap_span = 0;          // as FastHostInfo::remap_span
+};
+
+// a.st: the device descriptor of a read stream (all share the columns); a.key / a.c1_* / a.c2_* / a.within are not
+// read. Tuples, carry and results as fast_seq_k, except that a carried row has 4 + nattr words, the last one its
+// stream. Sets fs.last_path = 8.
+int64_t fast_seq_ms(const FastArgs& a, const int32_t* sid, const MSeqPlan& p, int nattr, FastState& fs,
+                    FastCarry& carry, uint32_t* tuples_out, int64_t tuples_cap, Scratch& sc, hipStream_t s,
+                    FastTimings* tm = nullptr);
+
+// keys[i] = the partition key of row i (the key column of its own stream, as int64), 0 for a row that is not read: the
+// one key column remap_keys takes when an interleaved batch's keys become dense ids
+void mseq_gather_keys(int64_t n, const int32_t* sid, const MSeqPlan& p, int64_t* keys, hipStream_t s);
+
 // ---- internal: the bucket-stack pipeline (stack.hip), entered by fast_every_within_v2 after key pass 0 ----
 
 // Facts about a batch once key pass 0 has scattered its 16-byte records {key - kmin | c1 << 31, ordinal - base,
@@ -155,9 +180,11 @@ int64_t stack_pipeline(const StackPlan& p, const FastArgs& a, const FastHostInfo
                        uint32_t* pairs_out, int64_t pairs_cap, Scratch& sc, hipStream_t s, FastTimings* tm);
 
 // Carry-out candidates (4 words each: key, global ordinal, event time, source = batch row >= 0 or -(old carry
-// row) - 1) → the new carry rows, sorted by (key, ordinal). `old` is read before carry.rows is replaced.
+// row) - 1) → the new carry rows, sorted by (key, ordinal). `old` is read before carry.rows is replaced. row_stream
+// (the stream of every batch row, fast_seq_ms only): the rows are one word wider, the last word the row's stream.
 void build_carry(const int64_t* cand, int64_t ncand, const NfaStream* st, int nattr, FastCarry& carry, Scratch& sc,
-                 hipStream_t s, int key_bits = 64, int64_t kmin = 0, bool key_runs_ordered = false);
+                 hipStream_t s, int key_bits = 64, int64_t kmin = 0, bool key_runs_ordered = false,
+                 const int32_t* row_stream = nullptr);
 
 // On-device projection of m closed-form outputs (pairs = the device tuples of the last batch): the query's select
 // programs (blob_dev = its device plan) → out[k * nsel + a], and e2's event time → ts_out[k] (may be null). An e1

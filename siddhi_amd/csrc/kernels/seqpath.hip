@@ -7,7 +7,9 @@
 //   emit    tile counts (from the link pass in row order, seq_count_kernel after a key sort), their scan, then the
 //           pairs in row order; each e2 has at most one pair, so this is the reference's order and nothing is sorted
 //   carry   one row per key whose last event passes c1 (build_carry); keys without events keep their row
+// Further down: the k-state sibling (fast_seq_k) and the same form over several streams (fast_seq_ms, mseq_dev.h).
 #include "fastpath.h"
+#include "mseq_dev.h"
 #include "seq_dev.h"
 
 namespace sm {
@@ -438,6 +440,250 @@ int64_t fast_seq_k(const FastArgs& a, const SeqKPlan& p, const FastHostInfo& hi,
   carry.ts_last = carry.active ? std::max<int64_t>(carry.ts_last, h.ts_last) : (int64_t)h.ts_last;
   carry.active = true;
   fs.last_path = 7;
+  if (tm) SM_HIP(hipEventRecord(tm->ev[3], s));
+  sc.used = mark;
+  return m;
+}
+
+namespace {
+
+__global__ void mseq_carry_check_kernel(const int64_t* __restrict__ rows, int64_t nc, int cw, int64_t obase,
+                                        MSeqFacts* __restrict__ f) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= nc) return;
+  const int64_t o = rows[c * cw + 1] - obase;
+  if (o >= 0 || o <= (int64_t)INT32_MIN) atomicOr(&f->bad_carry, 1u);
+}
+
+__global__ void mseq_keys_kernel(MSeqSrc s, int64_t* __restrict__ keys) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= s.n) return;
+  const int32_t sd = s.sid[i];
+  keys[i] = mseq_read(s, sd) ? mseq_key(s, sd, i) : 0;
+}
+
+MSeqSrc mseq_src(int64_t n, const int32_t* sid, const MSeqPlan& p) {
+  MSeqSrc src{};
+  src.n = n;
+  src.sid = sid;
+  src.read = p.read;
+  for (int q = 0; q < kMSeqStreams; ++q) src.kcol[q] = p.keyed ? p.kcol[q] : nullptr;
+  src.wide = p.wide;
+  return src;
+}
+
+}  // namespace
+
+void mseq_gather_keys(int64_t n, const int32_t* sid, const MSeqPlan& p, int64_t* keys, hipStream_t s) {
+  if (n > 0) hipLaunchKernelGGL(mseq_keys_kernel, seq_grid(n, 256), dim3(256), 0, s, mseq_src(n, sid, p), keys);
+}
+
+// The same form over several streams of one schema on an interleaved batch (mseq_dev.h). Per batch:
+//   mseq_facts   read rows per tile; over the read rows: key range, decreasing event time, ordinals (the only host round
+//                trip before anything is changed)
+//   mseq_pack    the read rows in row order as (key - kmin, row) sort pairs + a stream byte per packed position
+//                (skipped when every row is read and the query is unkeyed)
+//   mseq_sort    keyed: the stable LSD sort of the pairs, then the stream byte of every sorted position
+//   mseq_link    stream bytes, withins, conditions: hit and predecessor link at every read row, carry-out candidates
+//   mseq_keep / mseq_count / mseq_scan / mseq_emit / mseq_carry   as fast_seq_k, k = 2 included
+int64_t fast_seq_ms(const FastArgs& a, const int32_t* sid, const MSeqPlan& p, int nattr, FastState& fs,
+                    FastCarry& carry, uint32_t* tuples_out, int64_t tuples_cap, Scratch& sc, hipStream_t s,
+                    FastTimings* tm) {
+  const int64_t n = a.n;
+  const int k = p.k;
+  if (k < 2 || k > kSeqKMax) return FAST_OUTSIDE;
+  if (n == 0) return 0;
+  if (n >= 0x7fffffffll) return FAST_OUTSIDE;
+  const bool keyed = p.keyed;
+  const size_t mark = sc.used;
+  if (tm) {  // (the entry point's own marks come first: the first label here times from the last of them)
+    SM_HIP(hipEventRecord(tm->ev[0], s));
+    if (tm->nmk == 0) tm->mark("start", s);
+  }
+  auto tmark = [&](const char* l) {
+    if (tm) tm->mark(l, s);
+  };
+  const int cw = 4 + nattr;
+  const int64_t nc = carry.n;
+  bool any_within = false;
+  for (int m = 1; m < k; ++m) any_within |= p.within[m] >= 0;
+  const int64_t ntiles = (n + kSeqTile - 1) / kSeqTile;
+
+  MSeqSrc src = mseq_src(n, sid, p);
+  src.ts = a.ts;
+  src.ordinals = a.ordinals;
+  src.obase = a.ordinal_base;
+
+  // ---- facts: nothing is changed before they are read
+  MSeqFacts* f = (MSeqFacts*)sc.take(sizeof(MSeqFacts));
+  uint32_t* tile_n = (uint32_t*)sc.take((size_t)(ntiles + 1) * 4);
+  SM_HIP(hipMemsetAsync(f, 0, sizeof(MSeqFacts), s));
+  hipLaunchKernelGGL(mseq_facts_kernel, dim3((unsigned)std::min<int64_t>(ntiles, 2048)), dim3(kSeqBlock), 0, s, src,
+                     ntiles, tile_n, f);
+  if (nc > 0)
+    hipLaunchKernelGGL(mseq_carry_check_kernel, seq_grid(nc, 256), dim3(256), 0, s, (const int64_t*)carry.rows, nc,
+                       carry.width, a.ordinal_base, f);
+  tmark("mseq_facts");
+  MSeqFacts h;
+  SM_HIP(hipMemcpyAsync(&h, f, sizeof(MSeqFacts), hipMemcpyDeviceToHost, s));
+  SM_HIP(hipStreamSynchronize(s));
+  auto leave = [&](int64_t r) {
+    sc.used = mark;
+    return r;
+  };
+  constexpr uint64_t kBias = 0x8000000000000000ull;
+  const int64_t np = (int64_t)h.nread;
+  const int64_t ts0 = (int64_t)(~h.tmin_c ^ kBias), ts_last = (int64_t)(h.tmax ^ kBias);
+  const int64_t o0 = (int64_t)(~h.omin_c ^ kBias), omax = (int64_t)(h.omax ^ kBias);
+  if (any_within && np > 0 && (h.bad_ts || (carry.active && ts0 < carry.ts_last))) return leave(FAST_NON_MONOTONE);
+  if (h.bad_ord || h.bad_carry || (np > 0 && (o0 < 0 || omax >= 0x7fffffffll))) return leave(FAST_OUTSIDE);
+  if (nc > 0 && carry.width != cw) return leave(FAST_OUTSIDE);
+  if (np > tuples_cap) return leave(FAST_OUTSIDE);
+  if (np == 0) {  // no row of a stream the query reads: its carried rows wait
+    fs.last_path = 8;
+    return leave(0);
+  }
+  int64_t kmin = 0, kmax = 0;
+  int kbits = 0;
+  if (keyed) {
+    kmin = (int64_t)(~h.kmin_c ^ kBias);
+    kmax = (int64_t)(h.kmax ^ kBias);
+    const uint64_t kspan = (uint64_t)(kmax - kmin);
+    kbits = std::max(1, bits_of(kspan));
+    if (!carry.active && p.remap_span > 0 && (kbits > 30 || kspan > (uint64_t)p.remap_span)) return leave(FAST_KEY_SPAN);
+  }
+  const bool wide = kbits > 32;
+  const bool packed = keyed || np < n;
+
+  // what the carry-out reads lies first, so that the rest is free again when build_carry runs
+  const int64_t cand_cap = np + nc;
+  const int64_t ptiles = (np + kSeqTile - 1) / kSeqTile;
+  {  // scratch for the worst case, before anything changes
+    const uint64_t runs = keyed ? (kbits >= 62 ? (uint64_t)np : std::min<uint64_t>((uint64_t)np, (1ull << kbits))) : 1;
+    const uint64_t ncand_max = std::min<uint64_t>((uint64_t)np, runs * (uint64_t)(k - 1)) + (uint64_t)nc;
+    // per read row: sort pairs twice over (+ a histogram word per 4 events) and a stream byte; per row: link and hit
+    const size_t link = (size_t)np * (keyed ? (wide ? 26 : 18) : 5) + (size_t)n * 5 + (size_t)(ntiles + 2) * 8 + (8 << 20);
+    const size_t build = (size_t)ncand_max * (size_t)(8 * cw + 44) + (8 << 20);
+    if (sc.used + (size_t)cand_cap * 32 + std::max(link, build) + 4096 > sc.cap) return leave(FAST_OUTSIDE);
+  }
+  uint32_t* ctl = (uint32_t*)sc.take(8);  // [0] candidates, [1] tuples
+  int64_t* cand = (int64_t*)sc.take((size_t)cand_cap * 32);
+  const size_t keep = sc.used;
+
+  // ---- the read rows, then (keyed) in (key, arrival) order
+  const uint32_t* perm = nullptr;
+  const void* skey = nullptr;
+  const uint8_t* sstr = nullptr;
+  if (packed) {
+    exclusive_scan_u32(tile_n, (size_t)ntiles, sc, s);
+    MSeqPack pa{};
+    pa.s = src;
+    pa.tile_off = tile_n;
+    pa.kmin = kmin;
+    uint32_t* prow = (uint32_t*)sc.take((size_t)np * 4);
+    pa.prow = prow;
+    if (keyed) {
+      const size_t kb = wide ? 8 : 4;
+      void* pkey = sc.take((size_t)np * kb);
+      void* pkey2 = sc.take((size_t)np * kb);
+      uint32_t* prow2 = (uint32_t*)sc.take((size_t)np * 4);
+      uint8_t* ss = (uint8_t*)sc.take((size_t)np);
+      pa.pkey = pkey;
+      bool alt;
+      if (wide) {
+        hipLaunchKernelGGL(mseq_pack_kernel<uint64_t>, dim3((unsigned)ntiles), dim3(kSeqBlock), 0, s, pa);
+        tmark("mseq_pack");
+        alt = radix_sort_pairs<uint64_t>((uint64_t*)pkey, (uint64_t*)pkey2, prow, prow2, (size_t)np, 0, kbits, sc, s);
+      } else {
+        hipLaunchKernelGGL(mseq_pack_kernel<uint32_t>, dim3((unsigned)ntiles), dim3(kSeqBlock), 0, s, pa);
+        tmark("mseq_pack");
+        alt = radix_sort_pairs<uint32_t>((uint32_t*)pkey, (uint32_t*)pkey2, prow, prow2, (size_t)np, 0, kbits, sc, s);
+      }
+      skey = alt ? pkey2 : pkey;
+      perm = alt ? prow2 : prow;
+      hipLaunchKernelGGL(mseq_streams_kernel, seq_grid(np, kSeqBlock), dim3(kSeqBlock), 0, s, perm, sid, np, ss);
+      sstr = ss;
+      tmark("mseq_sort");
+    } else {
+      uint8_t* ss = (uint8_t*)sc.take((size_t)np);
+      pa.pstr = ss;
+      hipLaunchKernelGGL(mseq_pack_kernel<uint32_t>, dim3((unsigned)ntiles), dim3(kSeqBlock), 0, s, pa);
+      tmark("mseq_pack");
+      perm = prow;
+      sstr = ss;
+    }
+  }
+  if (tm) SM_HIP(hipEventRecord(tm->ev[1], s));
+
+  // ---- link
+  SM_HIP(hipMemsetAsync(ctl, 0, 8, s));
+  MSeqArgs ma{};
+  SeqKArgs& sa = ma.q;
+  sa.n = np;
+  sa.ts = a.ts;
+  sa.st = a.st;
+  sa.code = a.code;
+  sa.consts = a.consts;
+  sa.k = k;
+  for (int m = 0; m < kSeqKMax; ++m) {
+    sa.off[m] = m < k ? p.off[m] : 0;
+    sa.len[m] = m < k ? p.len[m] : 0;
+    sa.within[m] = m > 0 && m < k ? p.within[m] : -1;
+    ma.want[m] = m < k ? (uint8_t)p.stream[m] : 0;
+  }
+  sa.ordinals = a.ordinals;
+  sa.obase = a.ordinal_base;
+  sa.perm = perm;
+  sa.skey = skey;
+  sa.kmin = kmin;
+  sa.kmax = kmax;
+  sa.carry = (const int64_t*)carry.rows;
+  sa.nc = nc;
+  sa.cw = cw;
+  sa.prev = (int32_t*)sc.take((size_t)n * 4);
+  const size_t hit_bytes = ((size_t)n + 3) & ~(size_t)3;
+  sa.hit = (uint8_t*)sc.take(hit_bytes);
+  sa.cand = cand;
+  sa.cand_n = ctl;
+  ma.sstr = sstr;
+  ma.sid = sid;
+  uint32_t* counts = (uint32_t*)sc.take((size_t)(ntiles + 1) * 4);
+  if (packed) SM_HIP(hipMemsetAsync(sa.hit, 0, hit_bytes, s));  // rows that are not read have no lane
+  if (wide) hipLaunchKernelGGL(mseq_link_kernel<uint64_t>, dim3((unsigned)ptiles), dim3(kSeqBlock), 0, s, ma);
+  else hipLaunchKernelGGL(mseq_link_kernel<uint32_t>, dim3((unsigned)ptiles), dim3(kSeqBlock), 0, s, ma);
+  tmark("mseq_link");
+  if (nc > 0) {
+    if (wide) hipLaunchKernelGGL(seqk_keep_kernel<uint64_t>, seq_grid(nc, kSeqBlock), dim3(kSeqBlock), 0, s, sa);
+    else hipLaunchKernelGGL(seqk_keep_kernel<uint32_t>, seq_grid(nc, kSeqBlock), dim3(kSeqBlock), 0, s, sa);
+    tmark("mseq_keep");
+  }
+  if (tm) SM_HIP(hipEventRecord(tm->ev[2], s));
+
+  // ---- tuples in row order
+  hipLaunchKernelGGL(seqk_count_kernel, dim3((unsigned)ntiles), dim3(kSeqBlock), 0, s, (const uint8_t*)sa.hit, n, counts);
+  tmark("mseq_count");
+  exclusive_scan_u32(counts, (size_t)ntiles, sc, s, ctl + 1);
+  tmark("mseq_scan");
+  hipLaunchKernelGGL(seqk_emit_kernel, dim3((unsigned)ntiles), dim3(kSeqBlock), 0, s, (const uint8_t*)sa.hit,
+                     (const int32_t*)sa.prev, n, k, (const uint32_t*)counts, a.ordinals, a.ordinal_base,
+                     (const int64_t*)carry.rows, cw, tuples_out);
+  tmark("mseq_emit");
+  uint32_t hc[2] = {0, 0};
+  SM_HIP(hipMemcpyAsync(hc, ctl, 8, hipMemcpyDeviceToHost, s));
+  SM_HIP(hipStreamSynchronize(s));
+  const int64_t m = hc[1];
+  if (m > tuples_cap || (int64_t)hc[0] > cand_cap) {  // cannot happen (m <= np <= tuples_cap): checked, not assumed
+    sc.used = mark;
+    throw std::runtime_error("adjacent-run closed form over several streams: output larger than its buffer");
+  }
+
+  // ---- carry out (build_carry reads the old rows before it replaces them)
+  sc.used = keep;
+  build_carry(sa.cand, (int64_t)hc[0], a.st, nattr, carry, sc, s, 64, 0, false, sid);
+  tmark("mseq_carry");
+  carry.ts_last = carry.active ? std::max<int64_t>(carry.ts_last, ts_last) : ts_last;
+  carry.active = true;
+  fs.last_path = 8;
   if (tm) SM_HIP(hipEventRecord(tm->ev[3], s));
   sc.used = mark;
   return m;

@@ -723,7 +723,7 @@ __global__ void __launch_bounds__(kOB) stage_base_kernel(const uint32_t* __restr
 __global__ void carry_rows_kernel(const int64_t* __restrict__ cand, int64_t n, const NfaStream* __restrict__ st,
                                   int nattr, const int64_t* __restrict__ old, int w, int64_t kmin, int key_bits,
                                   int64_t* __restrict__ rows, uint64_t* __restrict__ kord, uint64_t* __restrict__ kkey,
-                                  uint32_t* __restrict__ idx) {
+                                  uint32_t* __restrict__ idx, const int32_t* __restrict__ sid) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int64_t* c = cand + 4 * i;
@@ -733,6 +733,7 @@ __global__ void carry_rows_kernel(const int64_t* __restrict__ cand, int64_t n, c
     r[1] = c[1];
     r[2] = c[2];
     for (int k = 0; k < nattr; ++k) r[3 + k] = (int64_t)canon(col_value(st, k, c[3]), st->types[k]);
+    if (sid) r[3 + nattr] = sid[c[3]];  // rows of an interleaved batch: the row's stream, one word more
   } else {  // a carried partial that stays pending: its row unchanged
     const int64_t* o = old + (-c[3] - 1) * w;
     for (int k = 0; k < w; ++k) r[k] = o[k];
@@ -784,8 +785,8 @@ void FastCarry::release() {
 }
 
 void build_carry(const int64_t* cand, int64_t ncand, const NfaStream* st, int nattr, FastCarry& carry, Scratch& sc,
-                 hipStream_t s, int key_bits, int64_t kmin, bool key_runs_ordered) {
-  const int w = 3 + nattr;
+                 hipStream_t s, int key_bits, int64_t kmin, bool key_runs_ordered, const int32_t* row_stream) {
+  const int w = 3 + nattr + (row_stream ? 1 : 0);
   if (ncand == 0) {
     carry.n = 0;
     carry.width = w;
@@ -799,7 +800,7 @@ void build_carry(const int64_t* cand, int64_t ncand, const NfaStream* st, int na
   uint32_t* idx = (uint32_t*)sc.take((size_t)ncand * 4);
   uint32_t* idx2 = (uint32_t*)sc.take((size_t)ncand * 4);
   hipLaunchKernelGGL(carry_rows_kernel, grid_of(ncand), dim3(256), 0, s, cand, ncand, st, nattr,
-                     (const int64_t*)carry.rows, w, kmin, key_bits, rows, kord, kkey, idx);
+                     (const int64_t*)carry.rows, w, kmin, key_bits, rows, kord, kkey, idx, row_stream);
   const uint32_t* fin;
   if (key_runs_ordered) {
     // every key's candidates are one run already in ordinal order: a stable sort by key (its significant bits) only

@@ -74,6 +74,7 @@ struct CarryCols {
   void* cols[kMaxAttrs];
   int64_t* ts;
   int64_t* ord;
+  int32_t* sid;  // or nullptr; else the rows' last word is their stream (fast_seq_ms): out, one per row
 };
 void carry_rows_to_columns(const int64_t* rows, int64_t n, const CarryCols& c, hipStream_t s);
 

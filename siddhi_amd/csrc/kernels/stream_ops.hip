@@ -1095,6 +1095,7 @@ __global__ void __launch_bounds__(256) carry_columns_kernel(const int64_t* __res
   const int64_t* row = rows + r * c.width;
   c.ord[r] = row[1];
   c.ts[r] = row[2];
+  if (c.sid) c.sid[r] = (int32_t)row[c.width - 1];
   for (int k = 0; k < c.nattr; ++k) {
     const int64_t v = row[3 + k];
     const int t = c.types[k];

@@ -460,6 +460,18 @@ bool seqk_progs_ok(const CompiledQuery& cq) {
   return true;
 }
 
+// The same check for a sequence over several streams (fast_seq_ms: seqpath.hip, mseq_dev.h).
+bool mseq_progs_ok(const CompiledQuery& cq) {
+  const Instr* code = (const Instr*)(cq.blob.data() + cq.hdr.off_code);
+  for (int m = 0; m < cq.fast_seq_ms; ++m)
+    for (int k = 0; k < cq.fast_ms_len[m]; ++k) {
+      const Instr& in = code[cq.fast_ms_off[m] + k];
+      if (in.op == OP_TS || in.op == OP_COL) return false;
+      if (in.op == OP_VAR && (in.a < 0 || in.a > m || !(in.b == 0 || in.b == -1))) return false;
+    }
+  return true;
+}
+
 }  // namespace
 }  // namespace sm
 
@@ -1243,10 +1255,10 @@ void read_outputs(sm_app* a, int qidx, const void* dev, int64_t n, std::vector<H
     const int64_t* rf = (const int64_t*)(b + sizeof(OutRec) + cq.hdr.nsel * sizeof(DVal));
     h.refs = rf;
     h.nrefs = cq.hdr.nrefs_vis;
-    if (cq.fast_seq_k) {  // k hidden refs: the match's events in slot order
+    if (cq.fast_seq_k || cq.fast_seq_ms) {  // k hidden refs: the match's events in slot order
       h.tuple = rf + cq.hdr.nrefs_vis;
       h.e1 = h.tuple[0];
-      h.e2 = h.tuple[cq.fast_seq_k - 1];
+      h.e2 = h.tuple[cq.match_arity() - 1];
     } else if (cq.fast_every_within || cq.fast_seq_adjacent) {  // two hidden refs: (e1, e2)
       h.e1 = rf[cq.hdr.nrefs_vis];
       h.e2 = rf[cq.hdr.nrefs_vis + 1];
@@ -1536,6 +1548,46 @@ size_t batch_scratch(const sm_app* a, int64_t N) {
   return (size_t)N * (100 + 8 * (size_t)lane_words) + (64 << 20);
 }
 
+// The outputs of an NFA run over a device batch (the first nc positions replayed carried rows) as the closed form
+// leaves them: the match tuples in dev_pairs, relative to ordinal_base and in reference order (from the plan's hidden
+// refs), and the outputs' Event data in nfa_proj for sm_app_device_project.
+void nfa_outs_to_device(sm_app* a, QueryRt& q, std::vector<HostOut>& outs, int64_t nc, int64_t ordinal_base,
+                        hipStream_t hs) {
+  std::stable_sort(outs.begin(), outs.end(), [](const HostOut& x, const HostOut& y) {
+    return x.r.pos != y.r.pos ? x.r.pos < y.r.pos : x.r.seq < y.r.seq;
+  });
+  const size_t ar = (size_t)q.cq.match_arity();  // 2, or k words per tuple for a k-state sequence
+  std::vector<uint32_t> pairs(outs.size() * ar);
+  for (size_t k = 0; k < outs.size(); ++k) {
+    if (outs[k].r.pos < nc || outs[k].e1 < 0 || outs[k].e2 < 0 || (ar > 2 && !outs[k].tuple))
+      throw std::runtime_error("query '" + q.cq.name + "': internal error in the hand-over of carried partials");
+    if (ar > 2) {
+      for (size_t m = 0; m < ar; ++m) pairs[ar * k + m] = (uint32_t)(outs[k].tuple[m] - ordinal_base);
+    } else {
+      pairs[2 * k] = (uint32_t)(outs[k].e1 - ordinal_base);
+      pairs[2 * k + 1] = (uint32_t)(outs[k].e2 - ordinal_base);
+    }
+  }
+  q.dev_pairs.ensure(std::max<size_t>(pairs.size() * 4, 16));
+  if (!pairs.empty())
+    SM_HIP(hipMemcpyAsync(q.dev_pairs.p, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice, hs));
+  // the outputs' Event data for sm_app_device_project (the closed form projects on demand; here the NFA kernel
+  // already evaluated the select list)
+  const size_t ns = (size_t)q.cq.hdr.nsel, m = outs.size();
+  std::vector<DVal> pv(m * ns);
+  std::vector<int64_t> pts(m);
+  for (size_t k = 0; k < m; ++k) {
+    if (ns) memcpy(pv.data() + k * ns, outs[k].vals, ns * sizeof(DVal));
+    pts[k] = outs[k].r.ts;
+  }
+  q.nfa_proj.ensure(std::max<size_t>(m * (ns * sizeof(DVal) + 8), 16));
+  if (m) {
+    if (ns) SM_HIP(hipMemcpyAsync(q.nfa_proj.p, pv.data(), m * ns * sizeof(DVal), hipMemcpyHostToDevice, hs));
+    SM_HIP(hipMemcpyAsync((char*)q.nfa_proj.p + m * ns * sizeof(DVal), pts.data(), m * 8, hipMemcpyHostToDevice, hs));
+  }
+  SM_HIP(hipStreamSynchronize(hs));
+}
+
 // A closed-form query handed to the general NFA kernel for the rest of its life (QueryRt::nfa_mode) when a device
 // batch leaves the closed form's premise: event time decreasing inside the batch or against the carried state,
 // a condition outside the v2 kernels' envelope with partials to carry, or matching state already held by the NFA
@@ -1635,45 +1687,98 @@ int64_t nfa_device_batch(sm_app* a, int qi, int s, size_t n, const int64_t* d_ts
     ~Reset() { f = false; }
   } reset_need{a->need_outs};
   run_pattern_query(a, qi, ev, N, outs, hs);
-  std::stable_sort(outs.begin(), outs.end(), [](const HostOut& x, const HostOut& y) {
-    return x.r.pos != y.r.pos ? x.r.pos < y.r.pos : x.r.seq < y.r.seq;
-  });
-  const size_t ar = (size_t)q.cq.match_arity();  // 2, or k words per tuple for a k-state sequence
-  std::vector<uint32_t> pairs(outs.size() * ar);
-  for (size_t k = 0; k < outs.size(); ++k) {
-    if (outs[k].r.pos < nc || outs[k].e1 < 0 || outs[k].e2 < 0 || (ar > 2 && !outs[k].tuple))
-      throw std::runtime_error("query '" + q.cq.name + "': internal error in the hand-over of carried partials");
-    if (ar > 2) {
-      for (size_t m = 0; m < ar; ++m) pairs[ar * k + m] = (uint32_t)(outs[k].tuple[m] - ordinal_base);
-    } else {
-      pairs[2 * k] = (uint32_t)(outs[k].e1 - ordinal_base);
-      pairs[2 * k + 1] = (uint32_t)(outs[k].e2 - ordinal_base);
-    }
-  }
-  q.dev_pairs.ensure(std::max<size_t>(pairs.size() * 4, 16));
-  if (!pairs.empty())
-    SM_HIP(hipMemcpyAsync(q.dev_pairs.p, pairs.data(), pairs.size() * 4, hipMemcpyHostToDevice, hs));
-  // the outputs' Event data for sm_app_device_project (the closed form projects on demand; here the NFA kernel
-  // already evaluated the select list)
-  const size_t ns = (size_t)q.cq.hdr.nsel, m = outs.size();
-  std::vector<DVal> pv(m * ns);
-  std::vector<int64_t> pts(m);
-  for (size_t k = 0; k < m; ++k) {
-    if (ns) memcpy(pv.data() + k * ns, outs[k].vals, ns * sizeof(DVal));
-    pts[k] = outs[k].r.ts;
-  }
-  q.nfa_proj.ensure(std::max<size_t>(m * (ns * sizeof(DVal) + 8), 16));
-  if (m) {
-    if (ns) SM_HIP(hipMemcpyAsync(q.nfa_proj.p, pv.data(), m * ns * sizeof(DVal), hipMemcpyHostToDevice, hs));
-    SM_HIP(hipMemcpyAsync((char*)q.nfa_proj.p + m * ns * sizeof(DVal), pts.data(), m * 8, hipMemcpyHostToDevice, hs));
-  }
-  SM_HIP(hipStreamSynchronize(hs));
+  nfa_outs_to_device(a, q, outs, nc, ordinal_base, hs);
+  const size_t m = outs.size();
   if (douts)  // the trigger of each output is its e2 (a data event): global ordinal as the delivery position
     for (HostOut& h : outs) {
       h.r.pos = h.e2;
       douts->push_back(h);
     }
   return (int64_t)m;
+}
+
+// The hand-over of a sequence over several streams (fast_seq_ms, seqpath.hip) from its closed form to the NFA kernel,
+// for good: each instance's carried rows (its last k - 1 read events at most, each with its stream in the row's last
+// word) are replayed on their own streams, every key's in ordinal order, as a batch of their own in front of whatever
+// comes next. Fewer than k events per instance emit nothing and leave the NFA in the state the rule implies (a
+// partial's life is one event, so the state is a function of the last k - 1 events). The playback clock is left alone,
+// as in nfa_device_batch. The caller's event-index arrays (d_ev_*, d_adv_*) are overwritten.
+void mseq_replay_carry(sm_app* a, int qi, hipStream_t hs) {
+  QueryRt& q = *a->queries[qi];
+  const int64_t nc = q.nfa_mode ? 0 : q.carry.n;
+  q.nfa_mode = true;
+  if (nc == 0) {
+    q.carry.reset();
+    return;
+  }
+  const int s0 = q.cq.streams.at(0);
+  const auto& attrs = a->streams[s0].def->attrs;
+  const int nattr = (int)attrs.size();
+  if (nattr > kMaxAttrs) throw std::runtime_error("stream has more attributes than the device path supports");
+  if (q.carry.width != 4 + nattr) throw std::runtime_error("query '" + q.cq.name + "': carried rows of another form");
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  size_t off = 0;
+  std::vector<size_t> col_off(nattr);
+  for (int k = 0; k < nattr; ++k) {
+    col_off[k] = off;
+    off += al((size_t)nc * width_of((int)attrs[k].type));
+  }
+  const size_t ts_off = off;
+  off += al((size_t)nc * 8);
+  const size_t ord_off = off;
+  off += al((size_t)nc * 8);
+  const size_t sid_off = off;
+  off += al((size_t)nc * 4);
+  a->d_rp.ensure(off);
+  char* base = (char*)a->d_rp.p;
+  CarryCols cc{};
+  cc.nattr = nattr;
+  cc.width = q.carry.width;
+  for (int k = 0; k < nattr; ++k) {
+    cc.types[k] = (int)attrs[k].type;
+    cc.cols[k] = base + col_off[k];
+  }
+  cc.ts = (int64_t*)(base + ts_off);
+  cc.ord = (int64_t*)(base + ord_off);
+  cc.sid = (int32_t*)(base + sid_off);
+  carry_rows_to_columns((const int64_t*)q.carry.rows, nc, cc, hs);
+  q.carry.reset();  // handed over below; a failure from here on marks the app failed
+  std::vector<NfaStream> nst(a->streams.size());
+  memset(nst.data(), 0, nst.size() * sizeof(NfaStream));
+  for (int s : q.cq.streams) {
+    nst[s].nattr = nattr;
+    for (int k = 0; k < nattr; ++k) {
+      nst[s].types[k] = (int)attrs[k].type;
+      nst[s].cols[k] = base + col_off[k];
+    }
+  }
+  a->d_rp_streams.ensure(nst.size() * sizeof(NfaStream));
+  SM_HIP(hipMemcpyAsync(a->d_rp_streams.p, nst.data(), nst.size() * sizeof(NfaStream), hipMemcpyHostToDevice, hs));
+  for (DBuf* d : {&a->d_ev_row, &a->d_ev_clock, &a->d_ev_ord, &a->d_adv_pos, &a->d_adv_clock, &a->d_adv_wall,
+                  &a->d_adv_upto})
+    d->ensure((size_t)nc * 8);
+  a->d_err.ensure(16);
+  a->d_count.ensure(16);
+  ensure_scratch(a, batch_scratch(a, nc));
+  a->sc.used = 0;
+  const int32_t* sid = (const int32_t*)(base + sid_off);
+  const int64_t* ts = (const int64_t*)(base + ts_off);
+  int64_t clock_out = a->clock;
+  const int64_t nadv = build_event_index(nc, sid, (int32_t)a->streams.size(), ts, (const int64_t*)(base + ord_off), 0,
+                                         a->ast.playback, a->clock, nullptr /* rows = positions */, (int64_t*)a->d_ev_ord.p,
+                                         (int64_t*)a->d_ev_clock.p, (int64_t*)a->d_adv_pos.p,
+                                         (int64_t*)a->d_adv_clock.p, (int64_t*)a->d_adv_wall.p,
+                                         (int64_t*)a->d_adv_upto.p, &clock_out, a->sc, hs);
+  const EvArrays ev{sid, nullptr, ts, (const int64_t*)a->d_ev_clock.p,
+                    (const int64_t*)a->d_ev_ord.p, (const NfaStream*)a->d_rp_streams.p, (const int64_t*)a->d_adv_pos.p,
+                    (const int64_t*)a->d_adv_clock.p, (const int64_t*)a->d_adv_wall.p, (const int64_t*)a->d_adv_upto.p,
+                    nadv, a->clock};
+  std::vector<HostOut> outs;
+  a->sc.used = 0;
+  const int64_t before = q.n_out;
+  run_pattern_query(a, qi, ev, nc, outs, hs);
+  if (q.n_out != before)
+    throw std::runtime_error("query '" + q.cq.name + "': internal error in the hand-over of carried rows");
 }
 
 // Whether anything takes query q's outputs: the collect dump, a StreamCallback on its output stream, or a
@@ -2670,6 +2775,104 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
   }
 }
 
+// The closed form of a sequence over several streams of one schema (CompiledQuery::fast_seq_ms; seqpath.hip
+// fast_seq_ms, path 8) over one interleaved device batch (sm_app_process_device_events): `nst` are the host copies of
+// the batch's stream descriptors, already uploaded to d_streams. Returns the number of matches (tuples in dev_pairs,
+// the projection state set as in device_batch_stream; the outputs that have consumers appended to draw), or
+// FAST_OUTSIDE / FAST_NON_MONOTONE with nothing changed.
+int64_t mseq_device_events(sm_app* a, int qi, size_t n, const int32_t* d_stream_idx, const int64_t* d_ts,
+                           const void* const* d_cols, const int64_t* d_ordinals, int64_t ordinal_base,
+                           const std::vector<NfaStream>& nst, hipStream_t hs, std::vector<DevOut>& draw) {
+  QueryRt& q = *a->queries[qi];
+  const CompiledQuery& cq = q.cq;
+  const int s0 = cq.streams.at(0);
+  const NfaStream& d = nst[s0];
+  const char* blob = (const char*)q.blob.p;
+  a->sc.used = 0;
+  FastArgs fa{};
+  fa.n = (int64_t)n;
+  fa.ts = d_ts;
+  fa.st = (const NfaStream*)a->d_streams.p + s0;
+  fa.code = (const Instr*)(blob + cq.hdr.off_code);
+  fa.consts = (const DVal*)(blob + cq.hdr.off_const);
+  fa.within = -1;
+  fa.ordinals = d_ordinals;
+  fa.ordinal_base = ordinal_base;
+  MSeqPlan mp;
+  mp.k = cq.fast_seq_ms;
+  for (int m = 0; m < mp.k; ++m) {
+    mp.stream[m] = cq.fast_ms_stream[m];
+    mp.off[m] = cq.fast_ms_off[m];
+    mp.len[m] = cq.fast_ms_len[m];
+    mp.within[m] = cq.fast_ms_within[m];
+  }
+  mp.keyed = cq.partition >= 0;
+  auto own_keys = [&] {  // every read stream's own key attribute
+    mp.wide = 0;
+    for (int s : cq.streams) {
+      mp.read |= 1ull << s;
+      if (!mp.keyed) continue;
+      const int c = cq.fast_ms_keycol.at(s);
+      mp.kcol[s] = d_cols[c];
+      if (d.types[c] == T_LONG) mp.wide |= 1ull << s;
+    }
+  };
+  own_keys();
+  auto dense_keys = [&] {  // the keys as dense ids (remap_keys), one int32 per row, read instead of the columns
+    int64_t* keys = (int64_t*)a->sc.take(n * 8);
+    int32_t* dk = (int32_t*)a->sc.take(n * 4);
+    mseq_gather_keys((int64_t)n, d_stream_idx, mp, keys, hs);
+    remap_keys(q.dense, keys, T_LONG, (int64_t)n, dk, hs);
+    for (int s : cq.streams) mp.kcol[s] = dk;
+    mp.wide = 0;
+  };
+  if (mp.keyed && n > 0) {  // as device_batch_stream: decided at the query's first closed-form batch, then kept
+    if (q.remap == 0 && !q.carry.active) {
+      if (a->key_remap >= 0) q.remap = a->key_remap ? 1 : 2;
+      else mp.remap_span = (int64_t)1 << 20;
+    }
+    if (q.remap == 1) dense_keys();
+  }
+  q.dev_pairs.ensure(std::max<size_t>(n * 4 * (size_t)mp.k, 16));
+  q.prev_carry_n = q.carry.n;
+  q.prev_carry_w = q.carry.width;
+  if (q.carry.n > 0) {
+    const size_t cb = (size_t)q.carry.n * q.carry.width * 8;
+    q.prev_carry.ensure(cb);
+    SM_HIP(hipMemcpyAsync(q.prev_carry.p, q.carry.rows, cb, hipMemcpyDeviceToDevice, hs));
+  }
+  FastTimings* tm = a->fast_timing ? &a->fast_tm : nullptr;
+  auto closed = [&] {
+    return fast_seq_ms(fa, d_stream_idx, mp, d.nattr, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, (int64_t)n, a->sc, hs,
+                       tm);
+  };
+  int64_t m = closed();
+  if (m == FAST_KEY_SPAN && q.remap != 1 && a->key_remap < 0 && mp.keyed) {
+    q.remap = 1;
+    mp.remap_span = 0;
+    remap_carry_keys(q.dense, q.carry.rows, q.carry.n, q.carry.width, a->sc, hs);
+    if (q.carry.n > 0)
+      SM_HIP(hipMemcpyAsync(q.prev_carry.p, q.carry.rows, (size_t)q.carry.n * q.carry.width * 8,
+                            hipMemcpyDeviceToDevice, hs));
+    dense_keys();
+    m = closed();
+  }
+  if (q.remap == 0 && mp.remap_span > 0 && m != FAST_OUTSIDE) q.remap = 2;  // the span fitted: values from here on
+  if (m < 0) return m == FAST_NON_MONOTONE ? m : (int64_t)FAST_OUTSIDE;
+  q.fast_path_used = q.fast.last_path;
+  q.proj_nfa = false;
+  q.proj_desc = d;
+  q.proj_ts = d_ts;
+  q.proj_ord = d_ordinals;
+  q.proj_base = ordinal_base;
+  q.proj_n = (int64_t)n;
+  q.dev_n = m;
+  q.proj_ok = true;
+  if (outputs_consumed(a, q)) device_outputs(a, qi, hs, draw);
+  else q.n_out += m;
+  return m;
+}
+
 // Outputs of device-batch queries to their consumers (deliver() hands them out even when only the collect dump
 // takes them).
 void deliver_device(sm_app* a, std::vector<HostOut>& douts, std::vector<DevOut>& draw) {
@@ -2919,6 +3122,14 @@ void flush(sm_app* a) {
       if (!closed_form(q.cq) || q.nfa_mode || q.nfa_used || q.carry.n == 0) continue;
       const int s = q.cq.streams.at(0);
       if (a->streams[s].rows > 0) nfa_device_batch(a, (int)qi, s, 0, nullptr, nullptr, nullptr, 0, a->stream, nullptr);
+    }
+    // likewise a sequence over several streams that ran its closed form on interleaved device batches (path 8)
+    for (size_t qi = 0; qi < a->queries.size(); ++qi) {
+      QueryRt& q = *a->queries[qi];
+      if (!q.cq.fast_seq_ms || q.nfa_mode || q.nfa_used || !q.carry.active) continue;
+      bool staged = false;
+      for (int s : q.cq.streams) staged |= a->streams[s].rows > 0;
+      if (staged) mseq_replay_carry(a, (int)qi, a->stream);
     }
     const EvHost e0{&a->ev_stream, &a->ev_row, &a->ev_ts, &a->ev_clock, &a->ev_ord, &a->adv_pos, &a->adv_clock,
                     &a->adv_wall};
@@ -3478,18 +3689,65 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
     a->d_streams.ensure(nst.size() * sizeof(NfaStream));
     SM_HIP(hipMemcpyAsync(a->d_streams.p, nst.data(), nst.size() * sizeof(NfaStream), hipMemcpyHostToDevice, hs));
     const int64_t N = (int64_t)n;
-    for (DBuf* d : {&a->d_ev_row, &a->d_ev_clock, &a->d_ev_ord, &a->d_adv_pos, &a->d_adv_clock, &a->d_adv_wall,
-                    &a->d_adv_upto})
-      d->ensure((size_t)N * 8);
     a->d_err.ensure(16);
     a->d_count.ensure(16);
-    ensure_scratch(a, batch_scratch(a, N));
+    // A sequence over several streams with a closed form (CompiledQuery::fast_seq_ms) takes it (path 8) when it is the
+    // app's only query: with more queries, deliver()'s order across queries is the NFA records' (position, query),
+    // which the closed form's per-query output arrays do not carry. Same-stream plans (fast_seq_adjacent, fast_seq_k)
+    // and every query under keep_outputs stay on the NFA kernel here, as before.
+    QueryRt* msq = nullptr;
+    if (a->queries.size() == 1 && a->queries[0]->cq.fast_seq_ms > 0 && a->streams.size() <= 64) msq = a->queries[0].get();
+    size_t need = batch_scratch(a, N);
+    if (msq) {  // as device_batch_stream sizes it for the sequences of seqpath.hip (+ a key and an id per row)
+      const size_t nc = (size_t)msq->carry.n, wc = (size_t)std::max(msq->carry.width, 4);
+      need = std::max(need, n * 52 + (n + nc) * 32 + (std::min<size_t>(n, (size_t)1 << 24) + nc) * (48 + 8 * wc) +
+                                ((size_t)64 << 20));
+    }
+    ensure_scratch(a, need);
     a->sc.used = 0;
     FastTimings* tm = a->fast_timing ? &a->fast_tm : nullptr;
     if (tm) {
       tm->nmk = 0;
       tm->mark("start", hs);
     }
+    std::vector<HostOut> outs;
+    a->in_device_events = true;
+    struct Reset {
+      bool& f;
+      ~Reset() { f = false; }
+    } reset_in{a->in_device_events};
+    const bool ms_tuples = msq && !a->keep_outputs;  // the query's matches go to dev_pairs, whichever kernel runs it
+    if (msq) {
+      QueryRt& q = *msq;
+      try {
+        if (ms_tuples && !q.nfa_mode && !q.nfa_used && mseq_progs_ok(q.cq)) {
+          std::vector<HostOut> douts;
+          std::vector<DevOut> draw;
+          a->out_arena.clear();
+          q.n_out = 0;
+          q.ev_out_n = 0;
+          const int64_t m = mseq_device_events(a, 0, n, d_stream_idx, d_ts, d_cols, d_ordinals, ordinal_base, nst, hs, draw);
+          if (m >= 0) {  // the closed form leaves the playback clock alone, as on the device-batch path
+            if (!d_ordinals) a->next_ordinal = std::max<int64_t>(a->next_ordinal, ordinal_base + N);
+            deliver_device(a, douts, draw);
+            return;
+          }
+        }
+        // outside the envelope, event time not monotone under a `within`, or matching state already on the NFA: the
+        // NFA kernel takes the query over for good, its carried rows first (path 5 from here on)
+        if (!q.nfa_mode) mseq_replay_carry(a, 0, hs);
+      } catch (const std::exception& e) {
+        a->failed = true;
+        a->failed_why = std::string("a device batch failed half-way (") + e.what() +
+                        "); the matching state is inconsistent: restore a snapshot or reset the app";
+        throw;
+      }
+    }
+    for (DBuf* d : {&a->d_ev_row, &a->d_ev_clock, &a->d_ev_ord, &a->d_adv_pos, &a->d_adv_clock, &a->d_adv_wall,
+                    &a->d_adv_upto})
+      d->ensure((size_t)N * 8);
+    ensure_scratch(a, need);
+    a->sc.used = 0;
     int64_t clock_out = a->clock;
     const int64_t nadv = build_event_index(
         N, d_stream_idx, (int32_t)a->streams.size(), d_ts, d_ordinals, ordinal_base, a->ast.playback, a->clock,
@@ -3503,18 +3761,31 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
                       (const int64_t*)a->d_adv_pos.p,
                       (const int64_t*)a->d_adv_clock.p, (const int64_t*)a->d_adv_wall.p, (const int64_t*)a->d_adv_upto.p,
                       nadv, a->clock};
-    std::vector<HostOut> outs;
-    a->in_device_events = true;
-    struct Reset {
-      bool& f;
-      ~Reset() { f = false; }
-    } reset_in{a->in_device_events};
     for (size_t qi = 0; qi < a->queries.size(); ++qi) {
+      QueryRt& q = *a->queries[qi];
       a->sc.used = 0;
-      a->queries[qi]->n_out = 0;
-      a->queries[qi]->ev_out_n = 0;
+      q.n_out = 0;
+      q.ev_out_n = 0;
+      if (ms_tuples) {  // as nfa_device_batch: the records are read whoever consumes them, for the tuples
+        std::vector<HostOut> qouts;
+        const bool had = a->need_outs;
+        a->need_outs = true;
+        struct Reset {
+          bool& f;
+          bool v;
+          ~Reset() { f = v; }
+        } reset_need{a->need_outs, had};
+        run_pattern_query(a, (int)qi, ev, N, qouts, hs, tm);
+        nfa_outs_to_device(a, q, qouts, 0, ordinal_base, hs);
+        q.dev_n = (int64_t)qouts.size();
+        q.fast_path_used = 5;
+        q.proj_ok = false;
+        q.proj_nfa = true;
+        if (outputs_consumed(a, q)) outs.insert(outs.end(), qouts.begin(), qouts.end());
+        continue;
+      }
       run_pattern_query(a, (int)qi, ev, N, outs, hs, tm);
-      a->queries[qi]->dev_n = a->queries[qi]->n_out;
+      q.dev_n = q.n_out;
     }
     a->clock = clock_out;
     a->clock_batch_in = a->clock;

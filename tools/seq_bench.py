@@ -10,6 +10,12 @@ fast_timing. Each step starts from a fresh runtime state (option reset), as benc
     python tools/seq_bench.py --precompile              # CPU only: the NFA route's JIT kernels into the code cache
     python tools/seq_bench.py --query three ...         # the three-state query `every e1, e2, e3 within T` (three rising
                                                         # ticks) on the same stream: fast_path 7, the adjacent-run kernels
+    python tools/seq_bench.py --query streams ...       # `every e1=A[c1], e2=B[c2] within T` over two streams of the same
+                                                        # rows (a row's stream: a hash bit of its number), and with
+                                                        # --query streams3 the three-state `A, B, A`: fast_path 8. Both
+                                                        # routes are sm_app_process_device_events here: --route closed
+                                                        # with this library, --route nfa with the parent commit's
+                                                        # (SM_LIB_VARIANT), which runs the NFA kernel
 
 Step time is a host clock around work that ends in a device synchronise; a run without a GPU fails."""
 import argparse
@@ -29,9 +35,19 @@ QUERY = ("@info(name='q') from every e1=StockStream[price>20], e2=StockStream[pr
 QUERY3 = ("@info(name='q') from every e1=StockStream[price>20], e2=StockStream[price>e1.price], "
           "e3=StockStream[price>e2.price] within 1 sec "
           "select e1.timestamp as i, e2.timestamp as j, e3.timestamp as l insert into OutputStream;")
+ATTRS = "(symbol int, price double, volume long, timestamp long); "
+SCHEMA_AB = "define stream A " + ATTRS + "define stream B " + ATTRS
+QUERY_AB = ("@info(name='q') from every e1=A[price>20], e2=B[price>e1.price] within 1 sec "
+            "select e1.timestamp as i, e2.timestamp as j insert into OutputStream;")
+QUERY_ABA = ("@info(name='q') from every e1=A[price>20], e2=B[price>e1.price], e3=A[price>e2.price] within 1 sec "
+             "select e1.timestamp as i, e2.timestamp as j, e3.timestamp as l insert into OutputStream;")
 
 
 def apps(query):
+    if query in ("streams", "streams3"):
+        q = QUERY_ABA if query == "streams3" else QUERY_AB
+        return {"keyed": SCHEMA_AB + "partition with (symbol of A, symbol of B) begin " + q + " end;",
+                "unkeyed": SCHEMA_AB + q}
     q = QUERY3 if query == "three" else QUERY
     return {"keyed": SCHEMA + "partition with (symbol of StockStream) begin " + q + " end;", "unkeyed": SCHEMA + q}
 
@@ -39,6 +55,8 @@ def apps(query):
 APPS = apps("pair")
 LABELS = ["seq_facts", "seq_sort", "seq_link", "seq_keep", "seq_count", "seq_scan", "seq_emit", "seq_carry"]
 LABELS += ["seqk_" + l[4:] for l in LABELS]
+LABELS += ["event_index", "mseq_facts", "mseq_pack", "mseq_sort", "mseq_link", "mseq_keep", "mseq_count", "mseq_scan",
+           "mseq_emit", "mseq_carry"]
 
 
 def precompile(query):
@@ -75,7 +93,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--route", choices=["closed", "nfa"], default="closed")
     ap.add_argument("--forms", default="keyed,unkeyed")
-    ap.add_argument("--query", choices=["pair", "three"], default="pair")
+    ap.add_argument("--query", choices=["pair", "three", "streams", "streams3"], default="pair")
     ap.add_argument("--precompile", action="store_true")
     ap.add_argument("--precompile-one")
     a = ap.parse_args()
@@ -95,7 +113,12 @@ def main():
     n = int(a.events)
     sym, price, _, _, ts = bench.gen_stock(0, n, a.keys, a.ts_div, dev, bench.seed_for(4))
     ordinals = torch.arange(n, dtype=torch.int64, device=dev)  # the timestamp attribute = the event's ordinal
-    sidx = torch.zeros(n, dtype=torch.int32, device=dev) if a.route == "nfa" else None
+    streams = a.query in ("streams", "streams3")
+    sidx = torch.zeros(n, dtype=torch.int32, device=dev) if a.route == "nfa" or streams else None
+    if streams:  # a deterministic two-way stream index from the row number
+        x = ordinals * (0x9E3779B97F4A7C15 - (1 << 64))  # (wraps: a multiply-xorshift hash, one bit of it)
+        x = (x ^ (x >> 29)) * (0xBF58476D1CE4E5B9 - (1 << 64))
+        sidx = ((x >> 43) & 1).to(torch.int32)
     hs = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     build_id = _lib.lib().sm_build_id().decode()
     torch.cuda.synchronize()
@@ -106,7 +129,7 @@ def main():
         cols = [sym, price, price, ordinals]  # volume is not read: aliased
 
         def step():
-            if a.route == "nfa":
+            if a.route == "nfa" or streams:
                 app.set_option("reset", 1)
                 app.process_device_events(sidx, ts, cols, ordinals=ordinals, hip_stream=hs)
             else:
