@@ -215,6 +215,13 @@ int sm_app_process_device_batch(sm_app* app, const char* stream_id, size_t n, co
  * back under a `within`, ordinals that do not fit), or host events staged for one of its streams, hand the query to the
  * NFA kernel for good, its carried events replayed first ("nfa_state:<query>" = 1, "fast_path:<query>" = 5; the tuples
  * still go to the device). Same-stream sequences and apps of several queries run on the NFA kernel here, as before.
+ * The pattern over two of these streams, `every e1=A[c1] -> e2=B[c2] within T` (A and B distinct, the `within` on e2,
+ * none on e1 or on the whole pattern, no having; partitioned: both streams keyed by one INT / LONG attribute of their
+ * own), runs a closed form of its own under the same conditions ("fast_path:<query>" = 9, "match_arity:<query>" = 2):
+ * every A event passing c1 is completed by the first later B event of its partition instance that passes c2, if that
+ * event lies inside T; one B event may complete many, oldest e1 first. It carries the e1 events still open at the end
+ * of the batch, leaves the (e1, e2) pairs on the device in the reference's order and hands over to the NFA kernel as
+ * the sequence does, its carried e1 events replayed first. The same pattern without a `within` runs on the NFA kernel.
  * "output_events:<query>" (sm_app_get_stat) = output events of the last such batch; "nfa_kernel:<query>" = which NFA
  * kernel ran it (1 = query-specialised, 2 = interpreter, 0 = none yet). */
 int sm_app_process_device_events(sm_app* app, size_t n, const int32_t* d_stream_idx, const int64_t* d_timestamps,

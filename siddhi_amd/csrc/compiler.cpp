@@ -828,6 +828,45 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
         }
       }
     }
+    // ---- the pattern over two streams of one schema: every e1=A[c1] -> e2=B[c2] within T (kernels/mpat_dev.h). The
+    // within on e2 is part of the form: it bounds the open partials and every scan
+    if (q.input == InputKind::PATTERN && root_el->kind == StateKind::NEXT && !root_el->has_within && !q.having &&
+        root_el->a->kind == StateKind::EVERY && root_el->a->a->kind == StateKind::STREAM && !root_el->a->has_within &&
+        !root_el->a->a->has_within && root_el->b->kind == StateKind::STREAM && root_el->b->has_within &&
+        root_el->a->a->stream_id != root_el->b->stream_id && h.nslots == 2 && (int)pres.size() == 2) {
+      bool ok = pres[0].kind == PK_STREAM && pres[1].kind == PK_STREAM && pres[0].stateId == 0 && pres[1].stateId == 1;
+      for (size_t r = 0; ok && r < refs.size(); r += 2)
+        if (!(refs[r + 1] == 0 || refs[r + 1] == kCurrent)) ok = false;
+      std::vector<int> keycol(app.streams.size(), -1);
+      for (int m = 0; ok && m < 2; ++m) {
+        const int si = lw.metas[m].stream;
+        const StreamDef& d0 = app.streams[lw.metas[0].stream];
+        const StreamDef& d = app.streams[si];
+        ok = d.attrs.size() == d0.attrs.size();
+        for (size_t c = 0; ok && c < d.attrs.size(); ++c) ok = d.attrs[c].type == d0.attrs[c].type;
+        if (!ok || partition < 0) continue;
+        // partitioned: both streams keyed by one INT / LONG attribute of their own
+        ok = false;
+        for (auto& w : app.partitions[partition].with)
+          if (w.stream_id == d.id && w.key->kind == ExprKind::VAR && w.key->stream_ref.empty()) {
+            const int c = d.index_of(w.key->attr);
+            if (c >= 0 && (d.attrs[c].type == AttrType::INT || d.attrs[c].type == AttrType::LONG)) {
+              keycol[si] = c;
+              ok = true;
+            }
+          }
+      }
+      if (ok) {
+        cq.fast_pat_ms = true;
+        cq.fast_pat_keycol = keycol;
+        cq.fast_pat_within = root_el->b->within_ms;
+        for (int m = 0; m < 2; ++m) {
+          cq.fast_pat_stream[m] = lw.metas[m].stream;
+          cq.fast_pat_off[m] = pres[m].progOff;
+          cq.fast_pat_len[m] = pres[m].progLen;
+        }
+      }
+    }
   }
   h.npre = (int)pres.size();
   h.npost = (int)posts.size();
@@ -836,7 +875,7 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
   h.nwithin = (int)withins.size();
   h.nsel = (int)cq.sel_types.size();
   h.nrefs_vis = (int)refs.size() / 2;
-  if (cq.fast_every_within || cq.fast_seq_adjacent) {  // hidden (e1, e2) ordinals for the NFA fallback of device batches
+  if (cq.fast_every_within || cq.fast_seq_adjacent || cq.fast_pat_ms) {  // hidden (e1, e2) ordinals for the NFA fallback of device batches
     refs.insert(refs.end(), {0, 0, 1, 0});
   }
   for (int m = 0; m < cq.fast_seq_k; ++m) refs.insert(refs.end(), {m, 0});  // hidden (e1, ..., ek) ordinals, likewise

@@ -62,6 +62,16 @@ struct CompiledQuery {
   int fast_ms_off[8] = {0}, fast_ms_len[8] = {0};
   int64_t fast_ms_within[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
   std::vector<int> fast_ms_keycol;
+  // fast path: every e1=A[c1] -> e2=B[c2] within T over two streams of one schema (pattern: every A event passing c1
+  // waits for the first later B event of its partition instance that passes c2, inside T; kernels/mpat_dev.h). A mark of
+  // its own: such a query runs through the interleaved entry point only. fast_pat_stream = the app streams of e1 and
+  // e2, fast_pat_off / len their condition programs (state context), fast_pat_within = T (always >= 0),
+  // fast_pat_keycol[s] as fast_ms_keycol. The plan carries the hidden (e1, e2) ordinal refs after the visible ones.
+  bool fast_pat_ms = false;
+  int fast_pat_stream[2] = {0, 0};
+  int fast_pat_off[2] = {0, 0}, fast_pat_len[2] = {0, 0};
+  int64_t fast_pat_within = -1;
+  std::vector<int> fast_pat_keycol;
   // uint32 words per device match tuple: k, 2 for every other state query, 1 for a filter (its kept row)
   int match_arity() const { return hdr.kind == 0 ? 1 : fast_seq_k ? fast_seq_k : fast_seq_ms ? fast_seq_ms : 2; }
 };

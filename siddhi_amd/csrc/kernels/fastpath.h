@@ -143,6 +143,28 @@ int64_t fast_seq_ms(const FastArgs& a, const int32_t* sid, const MSeqPlan& p, in
                     FastCarry& carry, uint32_t* tuples_out, int64_t tuples_cap, Scratch& sc, hipStream_t s,
                     FastTimings* tm = nullptr);
 
+// The pattern `every e1=A[c1] -> e2=B[c2] within T` over two streams of one schema on an interleaved batch
+// (seqpath.hip, mpat_dev.h has the rule and the kernels). The fields shared with MSeqPlan mean what they mean there.
+struct MPatPlan {
+  int stream[2] = {0, 0};          // app stream of e1 and of e2
+  int off[2] = {0, 0}, len[2] = {0, 0};  // c1 and c2 (state context)
+  int64_t within = -1;
+  uint64_t read = 0;
+  bool keyed = false;
+  const void* kcol[64] = {nullptr};
+  uint64_t wide = 0;
+  int64_t remap_span = 0;
+};
+
+// a.st, `sid`, key_remap and FAST_KEY_SPAN as fast_seq_ms; pairs and their conventions as fast_every_within_v2: (e1, e2)
+// uint32 relative to a.ordinal_base, a carried e1 negative as int32, in order of (e2, e1); at most n + carry.n of them
+// (pairs_cap). The carry holds the open partials' e1 rows [key, ordinal, ts, attributes] sorted by (key, ordinal): every
+// unmatched e1 that the batch's last read event does not find expired. FAST_NON_MONOTONE: p.within >= 0 and the event
+// time of the read rows decreases inside the batch or against carry.ts_last. Both error results are returned before the
+// carry or pairs_out is touched. Sets fs.last_path = 9.
+int64_t fast_pat_ms(const FastArgs& a, const int32_t* sid, const MPatPlan& p, int nattr, FastState& fs, FastCarry& carry,
+                    uint32_t* pairs_out, int64_t pairs_cap, Scratch& sc, hipStream_t s, FastTimings* tm = nullptr);
+
 // keys[i] = the partition key of row i (the key column of its own stream, as int64), 0 for a row that is not read: the
 // one key column remap_keys takes when an interleaved batch's keys become dense ids
 void mseq_gather_keys(int64_t n, const int32_t* sid, const MSeqPlan& p, int64_t* keys, hipStream_t s);

@@ -7,8 +7,10 @@
 //   emit    tile counts (from the link pass in row order, seq_count_kernel after a key sort), their scan, then the
 //           pairs in row order; each e2 has at most one pair, so this is the reference's order and nothing is sorted
 //   carry   one row per key whose last event passes c1 (build_carry); keys without events keep their row
-// Further down: the k-state sibling (fast_seq_k) and the same form over several streams (fast_seq_ms, mseq_dev.h).
+// Further down: the k-state sibling (fast_seq_k), the same form over several streams (fast_seq_ms, mseq_dev.h) and the
+// pattern `every e1=A -> e2=B within T` over two streams (fast_pat_ms, mpat_dev.h).
 #include "fastpath.h"
+#include "mpat_dev.h"
 #include "mseq_dev.h"
 #include "seq_dev.h"
 
@@ -684,6 +686,232 @@ int64_t fast_seq_ms(const FastArgs& a, const int32_t* sid, const MSeqPlan& p, in
   carry.ts_last = carry.active ? std::max<int64_t>(carry.ts_last, ts_last) : ts_last;
   carry.active = true;
   fs.last_path = 8;
+  if (tm) SM_HIP(hipEventRecord(tm->ev[3], s));
+  sc.used = mark;
+  return m;
+}
+
+// The pattern `every e1=A[c1] -> e2=B[c2] within T` over two streams of one schema on an interleaved batch
+// (mpat_dev.h). Per batch:
+//   mpat_facts / mpat_pack / mpat_sort   as fast_seq_ms with R = {A, B}: the read rows in (key, arrival) order with a
+//                stream byte per sorted position (unkeyed: row order)
+//   mpat_link    every partial (carried rows, then A rows passing c1) scans forward in its key run for its e2; the result
+//                is written at the e1's own place; carry-out candidates
+//   mpat_count / mpat_scan / mpat_emit   (e2, e1) compacted in order of e1: carried rows in carry order, then row order
+//   mpat_order   a stable sort by e2 alone over the bits of the largest relative ordinal, then the (e1, e2) pairs: the
+//                reference's (e2, e1) order
+//   mpat_carry   build_carry in its general form (several rows per key, sorted by (key, ordinal))
+// One host round trip for the facts and one for the two counts; nothing is changed before the second.
+int64_t fast_pat_ms(const FastArgs& a, const int32_t* sid, const MPatPlan& p, int nattr, FastState& fs, FastCarry& carry,
+                    uint32_t* pairs_out, int64_t pairs_cap, Scratch& sc, hipStream_t s, FastTimings* tm) {
+  const int64_t n = a.n;
+  if (n == 0) return 0;
+  const int64_t nc = carry.n;
+  if (n >= 0x7fffffffll || n + nc >= 0x7fffffffll) return FAST_OUTSIDE;
+  if (p.stream[0] < 0 || p.stream[0] >= kMSeqStreams || p.stream[1] < 0 || p.stream[1] >= kMSeqStreams)
+    return FAST_OUTSIDE;
+  const bool keyed = p.keyed;
+  const size_t mark = sc.used;
+  if (tm) {  // (the entry point's own marks come first: the first label here times from the last of them)
+    SM_HIP(hipEventRecord(tm->ev[0], s));
+    if (tm->nmk == 0) tm->mark("start", s);
+  }
+  auto tmark = [&](const char* l) {
+    if (tm) tm->mark(l, s);
+  };
+  const int cw = 3 + nattr;
+  const int64_t ntiles = (n + kSeqTile - 1) / kSeqTile;
+
+  MSeqSrc src{};
+  src.n = n;
+  src.sid = sid;
+  src.read = p.read;
+  for (int q = 0; q < kMSeqStreams; ++q) src.kcol[q] = keyed ? p.kcol[q] : nullptr;
+  src.wide = p.wide;
+  src.ts = a.ts;
+  src.ordinals = a.ordinals;
+  src.obase = a.ordinal_base;
+
+  // ---- facts: nothing is changed before they are read
+  MSeqFacts* f = (MSeqFacts*)sc.take(sizeof(MSeqFacts));
+  uint32_t* tile_n = (uint32_t*)sc.take((size_t)(ntiles + 1) * 4);
+  SM_HIP(hipMemsetAsync(f, 0, sizeof(MSeqFacts), s));
+  hipLaunchKernelGGL(mseq_facts_kernel, dim3((unsigned)std::min<int64_t>(ntiles, 2048)), dim3(kSeqBlock), 0, s, src,
+                     ntiles, tile_n, f);
+  if (nc > 0)
+    hipLaunchKernelGGL(mseq_carry_check_kernel, seq_grid(nc, 256), dim3(256), 0, s, (const int64_t*)carry.rows, nc,
+                       carry.width, a.ordinal_base, f);
+  tmark("mpat_facts");
+  MSeqFacts h;
+  SM_HIP(hipMemcpyAsync(&h, f, sizeof(MSeqFacts), hipMemcpyDeviceToHost, s));
+  SM_HIP(hipStreamSynchronize(s));
+  auto leave = [&](int64_t r) {
+    sc.used = mark;
+    return r;
+  };
+  constexpr uint64_t kBias = 0x8000000000000000ull;
+  const int64_t np = (int64_t)h.nread;
+  const int64_t ts0 = (int64_t)(~h.tmin_c ^ kBias), ts_last = (int64_t)(h.tmax ^ kBias);
+  const int64_t o0 = (int64_t)(~h.omin_c ^ kBias), omax = (int64_t)(h.omax ^ kBias);
+  // a partial older than T is dropped, and a scan ends at the window, only because event time never goes back
+  if (p.within >= 0 && np > 0 && (h.bad_ts || (carry.active && ts0 < carry.ts_last))) return leave(FAST_NON_MONOTONE);
+  if (h.bad_ord || h.bad_carry || (np > 0 && (o0 < 0 || omax >= 0x7fffffffll))) return leave(FAST_OUTSIDE);
+  if (nc > 0 && carry.width != cw) return leave(FAST_OUTSIDE);
+  if (np + nc > pairs_cap) return leave(FAST_OUTSIDE);
+  if (np == 0) {  // no row of a stream the query reads: its carried rows wait
+    fs.last_path = 9;
+    return leave(0);
+  }
+  int64_t kmin = 0, kmax = 0;
+  int kbits = 0;
+  if (keyed) {
+    kmin = (int64_t)(~h.kmin_c ^ kBias);
+    kmax = (int64_t)(h.kmax ^ kBias);
+    const uint64_t kspan = (uint64_t)(kmax - kmin);
+    kbits = std::max(1, bits_of(kspan));
+    if (!carry.active && p.remap_span > 0 && (kbits > 30 || kspan > (uint64_t)p.remap_span)) return leave(FAST_KEY_SPAN);
+  }
+  const bool wide = kbits > 32;
+  const bool packed = keyed || np < n;
+
+  // what the carry-out reads lies first, so that the rest is free again when build_carry runs
+  const int64_t cand_cap = np + nc;
+  const int64_t total = nc + n;  // entries of `res`
+  const int64_t rtiles = (total + kSeqTile - 1) / kSeqTile;
+  const size_t hist = (size_t)8 << 20;
+  {  // scratch up to the counts, for the worst case, before anything changes. Per read row: sort pairs twice over (+ a
+     // histogram word per 4 rows) and a stream byte, then the (e2, e1) sort pairs twice over; per entry of res: 4 bytes
+    const size_t link = (size_t)np * (keyed ? (wide ? 43 : 35) : 22) + (size_t)nc * 17 + (size_t)total * 4 +
+                        (size_t)(ntiles + rtiles + 4) * 8 + hist;
+    if (sc.used + (size_t)cand_cap * 32 + link + 4096 > sc.cap) return leave(FAST_OUTSIDE);
+  }
+  uint32_t* ctl = (uint32_t*)sc.take(8);  // [0] candidates, [1] pairs
+  int64_t* cand = (int64_t*)sc.take((size_t)cand_cap * 32);
+  const size_t keep = sc.used;
+
+  // ---- the read rows, then (keyed) in (key, arrival) order
+  const uint32_t* perm = nullptr;
+  const void* skey = nullptr;
+  const uint8_t* sstr = nullptr;
+  if (packed) {
+    exclusive_scan_u32(tile_n, (size_t)ntiles, sc, s);
+    MSeqPack pa{};
+    pa.s = src;
+    pa.tile_off = tile_n;
+    pa.kmin = kmin;
+    uint32_t* prow = (uint32_t*)sc.take((size_t)np * 4);
+    pa.prow = prow;
+    if (keyed) {
+      const size_t kb = wide ? 8 : 4;
+      void* pkey = sc.take((size_t)np * kb);
+      void* pkey2 = sc.take((size_t)np * kb);
+      uint32_t* prow2 = (uint32_t*)sc.take((size_t)np * 4);
+      uint8_t* ss = (uint8_t*)sc.take((size_t)np);
+      pa.pkey = pkey;
+      bool alt;
+      if (wide) {
+        hipLaunchKernelGGL(mseq_pack_kernel<uint64_t>, dim3((unsigned)ntiles), dim3(kSeqBlock), 0, s, pa);
+        tmark("mpat_pack");
+        alt = radix_sort_pairs<uint64_t>((uint64_t*)pkey, (uint64_t*)pkey2, prow, prow2, (size_t)np, 0, kbits, sc, s);
+      } else {
+        hipLaunchKernelGGL(mseq_pack_kernel<uint32_t>, dim3((unsigned)ntiles), dim3(kSeqBlock), 0, s, pa);
+        tmark("mpat_pack");
+        alt = radix_sort_pairs<uint32_t>((uint32_t*)pkey, (uint32_t*)pkey2, prow, prow2, (size_t)np, 0, kbits, sc, s);
+      }
+      skey = alt ? pkey2 : pkey;
+      perm = alt ? prow2 : prow;
+      hipLaunchKernelGGL(mseq_streams_kernel, seq_grid(np, kSeqBlock), dim3(kSeqBlock), 0, s, perm, sid, np, ss);
+      sstr = ss;
+      tmark("mpat_sort");
+    } else {
+      uint8_t* ss = (uint8_t*)sc.take((size_t)np);
+      pa.pstr = ss;
+      hipLaunchKernelGGL(mseq_pack_kernel<uint32_t>, dim3((unsigned)ntiles), dim3(kSeqBlock), 0, s, pa);
+      tmark("mpat_pack");
+      perm = prow;
+      sstr = ss;
+    }
+  }
+  if (tm) SM_HIP(hipEventRecord(tm->ev[1], s));
+
+  // ---- link
+  SM_HIP(hipMemsetAsync(ctl, 0, 8, s));
+  MPatArgs ma{};
+  ma.np = np;
+  ma.n = n;
+  ma.ts = a.ts;
+  ma.st = a.st;
+  ma.code = a.code;
+  ma.consts = a.consts;
+  ma.c1_off = p.off[0];
+  ma.c1_len = p.len[0];
+  ma.c2_off = p.off[1];
+  ma.c2_len = p.len[1];
+  ma.within = p.within;
+  ma.ts_last = ts_last;
+  ma.ordinals = a.ordinals;
+  ma.obase = a.ordinal_base;
+  ma.perm = perm;
+  ma.skey = skey;
+  ma.kmin = kmin;
+  ma.kmax = kmax;
+  ma.sstr = sstr;
+  ma.sid = sid;
+  ma.sa = p.stream[0];
+  ma.sb = p.stream[1];
+  ma.carry = (const int64_t*)carry.rows;
+  ma.nc = nc;
+  ma.cw = cw;
+  ma.res = (int32_t*)sc.take((size_t)total * 4);
+  ma.cand = cand;
+  ma.cand_n = ctl;
+  uint32_t* counts = (uint32_t*)sc.take((size_t)(rtiles + 1) * 4);
+  // rows that are not read have no lane: their entries are "none"
+  if (np < n) SM_HIP(hipMemsetD32Async((hipDeviceptr_t)(ma.res + nc), (int)kSeqNone, (size_t)n, s));
+  const dim3 lgrid((unsigned)((nc + np + kSeqTile - 1) / kSeqTile));
+  if (wide) hipLaunchKernelGGL(mpat_link_kernel<uint64_t>, lgrid, dim3(kSeqBlock), 0, s, ma);
+  else hipLaunchKernelGGL(mpat_link_kernel<uint32_t>, lgrid, dim3(kSeqBlock), 0, s, ma);
+  tmark("mpat_link");
+  if (tm) SM_HIP(hipEventRecord(tm->ev[2], s));
+
+  // ---- the two counts: pairs and carry-out candidates
+  hipLaunchKernelGGL(seq_count_kernel, dim3((unsigned)rtiles), dim3(kSeqBlock), 0, s, (const int32_t*)ma.res, total, counts);
+  tmark("mpat_count");
+  exclusive_scan_u32(counts, (size_t)rtiles, sc, s, ctl + 1);
+  tmark("mpat_scan");
+  uint32_t hc[2] = {0, 0};
+  SM_HIP(hipMemcpyAsync(hc, ctl, 8, hipMemcpyDeviceToHost, s));
+  SM_HIP(hipStreamSynchronize(s));
+  const int64_t m = hc[1], ncand = hc[0];
+  if (m > pairs_cap || ncand > cand_cap) {  // cannot happen (one of each per partial at most): checked, not assumed
+    sc.used = mark;
+    throw std::runtime_error("pattern closed form over two streams: output larger than its buffer");
+  }
+  // room for the carry build, now that the number of candidates is known: still nothing is changed
+  if (keep + (size_t)ncand * (size_t)(8 * cw + 44) + hist + 4096 > sc.cap) return leave(FAST_OUTSIDE);
+
+  // ---- pairs in order of e1, then the stable sort by e2
+  if (m > 0) {
+    uint32_t* jk = (uint32_t*)sc.take((size_t)m * 4);
+    uint32_t* jk2 = (uint32_t*)sc.take((size_t)m * 4);
+    uint32_t* iv = (uint32_t*)sc.take((size_t)m * 4);
+    uint32_t* iv2 = (uint32_t*)sc.take((size_t)m * 4);
+    hipLaunchKernelGGL(mpat_emit_kernel, dim3((unsigned)rtiles), dim3(kSeqBlock), 0, s, (const int32_t*)ma.res, total, nc,
+                       (const uint32_t*)counts, a.ordinals, a.ordinal_base, (const int64_t*)carry.rows, cw, jk, iv);
+    tmark("mpat_emit");
+    const bool alt = radix_sort_pairs<uint32_t>(jk, jk2, iv, iv2, (size_t)m, 0, std::max(1, bits_of((uint64_t)omax)), sc, s);
+    hipLaunchKernelGGL(mpat_pairs_kernel, seq_grid(m, kSeqBlock), dim3(kSeqBlock), 0, s,
+                       (const uint32_t*)(alt ? jk2 : jk), (const uint32_t*)(alt ? iv2 : iv), m, pairs_out);
+    tmark("mpat_order");
+  }
+
+  // ---- carry out (build_carry reads the old rows before it replaces them)
+  sc.used = keep;
+  build_carry(cand, ncand, a.st, nattr, carry, sc, s);
+  tmark("mpat_carry");
+  carry.ts_last = carry.active ? std::max<int64_t>(carry.ts_last, ts_last) : ts_last;
+  carry.active = true;
+  fs.last_path = 9;
   if (tm) SM_HIP(hipEventRecord(tm->ev[3], s));
   sc.used = mark;
   return m;

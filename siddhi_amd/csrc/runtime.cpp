@@ -472,6 +472,19 @@ bool mseq_progs_ok(const CompiledQuery& cq) {
   return true;
 }
 
+// The same check for the pattern over two streams (fast_pat_ms: seqpath.hip, mpat_dev.h): c1 reads slot 0, c2 slots 0
+// and 1.
+bool mpat_progs_ok(const CompiledQuery& cq) {
+  const Instr* code = (const Instr*)(cq.blob.data() + cq.hdr.off_code);
+  for (int m = 0; m < 2; ++m)
+    for (int k = 0; k < cq.fast_pat_len[m]; ++k) {
+      const Instr& in = code[cq.fast_pat_off[m] + k];
+      if (in.op == OP_TS || in.op == OP_COL) return false;
+      if (in.op == OP_VAR && (in.a < 0 || in.a > m || !(in.b == 0 || in.b == -1))) return false;
+    }
+  return true;
+}
+
 }  // namespace
 }  // namespace sm
 
@@ -1259,7 +1272,7 @@ void read_outputs(sm_app* a, int qidx, const void* dev, int64_t n, std::vector<H
       h.tuple = rf + cq.hdr.nrefs_vis;
       h.e1 = h.tuple[0];
       h.e2 = h.tuple[cq.match_arity() - 1];
-    } else if (cq.fast_every_within || cq.fast_seq_adjacent) {  // two hidden refs: (e1, e2)
+    } else if (cq.fast_every_within || cq.fast_seq_adjacent || cq.fast_pat_ms) {  // two hidden refs: (e1, e2)
       h.e1 = rf[cq.hdr.nrefs_vis];
       h.e2 = rf[cq.hdr.nrefs_vis + 1];
     }
@@ -1715,7 +1728,11 @@ void mseq_replay_carry(sm_app* a, int qi, hipStream_t hs) {
   const auto& attrs = a->streams[s0].def->attrs;
   const int nattr = (int)attrs.size();
   if (nattr > kMaxAttrs) throw std::runtime_error("stream has more attributes than the device path supports");
-  if (q.carry.width != 4 + nattr) throw std::runtime_error("query '" + q.cq.name + "': carried rows of another form");
+  // the pattern over two streams (fast_pat_ms, path 9) carries open partials: e1 rows, all on e1's stream and without the
+  // stream word. Replayed in (key, ordinal) order they re-create their partials and emit nothing: no e2 is among them
+  const bool pat = q.cq.fast_pat_ms;
+  if (q.carry.width != (pat ? 3 : 4) + nattr)
+    throw std::runtime_error("query '" + q.cq.name + "': carried rows of another form");
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   size_t off = 0;
   std::vector<size_t> col_off(nattr);
@@ -1740,7 +1757,8 @@ void mseq_replay_carry(sm_app* a, int qi, hipStream_t hs) {
   }
   cc.ts = (int64_t*)(base + ts_off);
   cc.ord = (int64_t*)(base + ord_off);
-  cc.sid = (int32_t*)(base + sid_off);
+  cc.sid = pat ? nullptr : (int32_t*)(base + sid_off);
+  if (pat) SM_HIP(hipMemsetD32Async((hipDeviceptr_t)(base + sid_off), q.cq.fast_pat_stream[0], (size_t)nc, hs));
   carry_rows_to_columns((const int64_t*)q.carry.rows, nc, cc, hs);
   q.carry.reset();  // handed over below; a failure from here on marks the app failed
   std::vector<NfaStream> nst(a->streams.size());
@@ -2873,6 +2891,103 @@ int64_t mseq_device_events(sm_app* a, int qi, size_t n, const int32_t* d_stream_
   return m;
 }
 
+// The closed form of the pattern `every e1=A -> e2=B within T` over two streams of one schema
+// (CompiledQuery::fast_pat_ms; seqpath.hip fast_pat_ms, path 9) over one interleaved device batch: arguments and
+// results as mseq_device_events. After the match count it is the pattern branch: (e1, e2) pairs in dev_pairs, an e1
+// carried from an earlier batch projected from prev_carry.
+int64_t mpat_device_events(sm_app* a, int qi, size_t n, const int32_t* d_stream_idx, const int64_t* d_ts,
+                           const void* const* d_cols, const int64_t* d_ordinals, int64_t ordinal_base,
+                           const std::vector<NfaStream>& nst, hipStream_t hs, std::vector<DevOut>& draw) {
+  QueryRt& q = *a->queries[qi];
+  const CompiledQuery& cq = q.cq;
+  const int s0 = cq.fast_pat_stream[0];
+  const NfaStream& d = nst[s0];
+  const char* blob = (const char*)q.blob.p;
+  a->sc.used = 0;
+  FastArgs fa{};
+  fa.n = (int64_t)n;
+  fa.ts = d_ts;
+  fa.st = (const NfaStream*)a->d_streams.p + s0;
+  fa.code = (const Instr*)(blob + cq.hdr.off_code);
+  fa.consts = (const DVal*)(blob + cq.hdr.off_const);
+  fa.within = cq.fast_pat_within;
+  fa.ordinals = d_ordinals;
+  fa.ordinal_base = ordinal_base;
+  MPatPlan mp;
+  MSeqPlan kp;  // the key columns, for mseq_gather_keys
+  for (int m = 0; m < 2; ++m) {
+    mp.stream[m] = cq.fast_pat_stream[m];
+    mp.off[m] = cq.fast_pat_off[m];
+    mp.len[m] = cq.fast_pat_len[m];
+    mp.read |= 1ull << cq.fast_pat_stream[m];
+  }
+  mp.within = cq.fast_pat_within;
+  mp.keyed = cq.partition >= 0;
+  if (mp.keyed)
+    for (int m = 0; m < 2; ++m) {  // each stream's own key attribute
+      const int s = mp.stream[m], c = cq.fast_pat_keycol.at(s);
+      mp.kcol[s] = d_cols[c];
+      if (d.types[c] == T_LONG) mp.wide |= 1ull << s;
+    }
+  kp.read = mp.read;
+  kp.keyed = mp.keyed;
+  kp.wide = mp.wide;
+  for (int m = 0; m < 2; ++m) kp.kcol[mp.stream[m]] = mp.kcol[mp.stream[m]];
+  auto dense_keys = [&] {  // the keys as dense ids (remap_keys), one int32 per row, read instead of the columns
+    int64_t* keys = (int64_t*)a->sc.take(n * 8);
+    int32_t* dk = (int32_t*)a->sc.take(n * 4);
+    mseq_gather_keys((int64_t)n, d_stream_idx, kp, keys, hs);
+    remap_keys(q.dense, keys, T_LONG, (int64_t)n, dk, hs);
+    for (int m = 0; m < 2; ++m) mp.kcol[mp.stream[m]] = dk;
+    mp.wide = 0;
+  };
+  if (mp.keyed && n > 0) {  // as mseq_device_events: decided at the query's first closed-form batch, then kept
+    if (q.remap == 0 && !q.carry.active) {
+      if (a->key_remap >= 0) q.remap = a->key_remap ? 1 : 2;
+      else mp.remap_span = (int64_t)1 << 20;
+    }
+    if (q.remap == 1) dense_keys();
+  }
+  const int64_t cap = (int64_t)n + q.carry.n;
+  q.dev_pairs.ensure(std::max<size_t>((size_t)cap * 8, 16));
+  q.prev_carry_n = q.carry.n;
+  q.prev_carry_w = q.carry.width;
+  if (q.carry.n > 0) {
+    const size_t cb = (size_t)q.carry.n * q.carry.width * 8;
+    q.prev_carry.ensure(cb);
+    SM_HIP(hipMemcpyAsync(q.prev_carry.p, q.carry.rows, cb, hipMemcpyDeviceToDevice, hs));
+  }
+  FastTimings* tm = a->fast_timing ? &a->fast_tm : nullptr;
+  auto closed = [&] {
+    return fast_pat_ms(fa, d_stream_idx, mp, d.nattr, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, cap, a->sc, hs, tm);
+  };
+  int64_t m = closed();
+  if (m == FAST_KEY_SPAN && q.remap != 1 && a->key_remap < 0 && mp.keyed) {
+    q.remap = 1;
+    mp.remap_span = 0;
+    remap_carry_keys(q.dense, q.carry.rows, q.carry.n, q.carry.width, a->sc, hs);
+    if (q.carry.n > 0)
+      SM_HIP(hipMemcpyAsync(q.prev_carry.p, q.carry.rows, (size_t)q.carry.n * q.carry.width * 8,
+                            hipMemcpyDeviceToDevice, hs));
+    dense_keys();
+    m = closed();
+  }
+  if (q.remap == 0 && mp.remap_span > 0 && m != FAST_OUTSIDE) q.remap = 2;  // the span fitted: values from here on
+  if (m < 0) return m == FAST_NON_MONOTONE ? m : (int64_t)FAST_OUTSIDE;
+  q.fast_path_used = q.fast.last_path;
+  q.proj_nfa = false;
+  q.proj_desc = d;
+  q.proj_ts = d_ts;
+  q.proj_ord = d_ordinals;
+  q.proj_base = ordinal_base;
+  q.proj_n = (int64_t)n;
+  q.dev_n = m;
+  q.proj_ok = true;
+  if (outputs_consumed(a, q)) device_outputs(a, qi, hs, draw);
+  else q.n_out += m;
+  return m;
+}
+
 // Outputs of device-batch queries to their consumers (deliver() hands them out even when only the collect dump
 // takes them).
 void deliver_device(sm_app* a, std::vector<HostOut>& douts, std::vector<DevOut>& draw) {
@@ -3123,10 +3238,11 @@ void flush(sm_app* a) {
       const int s = q.cq.streams.at(0);
       if (a->streams[s].rows > 0) nfa_device_batch(a, (int)qi, s, 0, nullptr, nullptr, nullptr, 0, a->stream, nullptr);
     }
-    // likewise a sequence over several streams that ran its closed form on interleaved device batches (path 8)
+    // likewise a sequence or a pattern over several streams that ran its closed form on interleaved device batches
+    // (paths 8 and 9)
     for (size_t qi = 0; qi < a->queries.size(); ++qi) {
       QueryRt& q = *a->queries[qi];
-      if (!q.cq.fast_seq_ms || q.nfa_mode || q.nfa_used || !q.carry.active) continue;
+      if (!(q.cq.fast_seq_ms || q.cq.fast_pat_ms) || q.nfa_mode || q.nfa_used || !q.carry.active) continue;
       bool staged = false;
       for (int s : q.cq.streams) staged |= a->streams[s].rows > 0;
       if (staged) mseq_replay_carry(a, (int)qi, a->stream);
@@ -3696,12 +3812,18 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
     // which the closed form's per-query output arrays do not carry. Same-stream plans (fast_seq_adjacent, fast_seq_k)
     // and every query under keep_outputs stay on the NFA kernel here, as before.
     QueryRt* msq = nullptr;
-    if (a->queries.size() == 1 && a->queries[0]->cq.fast_seq_ms > 0 && a->streams.size() <= 64) msq = a->queries[0].get();
+    // Likewise the pattern `every e1=A -> e2=B within T` over two streams (CompiledQuery::fast_pat_ms, path 9).
+    if (a->queries.size() == 1 && (a->queries[0]->cq.fast_seq_ms > 0 || a->queries[0]->cq.fast_pat_ms) &&
+        a->streams.size() <= 64)
+      msq = a->queries[0].get();
     size_t need = batch_scratch(a, N);
     if (msq) {  // as device_batch_stream sizes it for the sequences of seqpath.hip (+ a key and an id per row)
       const size_t nc = (size_t)msq->carry.n, wc = (size_t)std::max(msq->carry.width, 4);
       need = std::max(need, n * 52 + (n + nc) * 32 + (std::min<size_t>(n, (size_t)1 << 24) + nc) * (48 + 8 * wc) +
                                 ((size_t)64 << 20));
+      // the pattern: a result word and two sort pairs per carried row too; its carry build is sized by the candidates
+      // the batch leaves (fast_pat_ms checks that before anything changes)
+      if (msq->cq.fast_pat_ms) need += nc * 24;
     }
     ensure_scratch(a, need);
     a->sc.used = 0;
@@ -3720,13 +3842,15 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
     if (msq) {
       QueryRt& q = *msq;
       try {
-        if (ms_tuples && !q.nfa_mode && !q.nfa_used && mseq_progs_ok(q.cq)) {
+        const bool pat = q.cq.fast_pat_ms;
+        if (ms_tuples && !q.nfa_mode && !q.nfa_used && (pat ? mpat_progs_ok(q.cq) : mseq_progs_ok(q.cq))) {
           std::vector<HostOut> douts;
           std::vector<DevOut> draw;
           a->out_arena.clear();
           q.n_out = 0;
           q.ev_out_n = 0;
-          const int64_t m = mseq_device_events(a, 0, n, d_stream_idx, d_ts, d_cols, d_ordinals, ordinal_base, nst, hs, draw);
+          const int64_t m = (pat ? mpat_device_events : mseq_device_events)(a, 0, n, d_stream_idx, d_ts, d_cols, d_ordinals,
+                                                                            ordinal_base, nst, hs, draw);
           if (m >= 0) {  // the closed form leaves the playback clock alone, as on the device-batch path
             if (!d_ordinals) a->next_ordinal = std::max<int64_t>(a->next_ordinal, ordinal_base + N);
             deliver_device(a, douts, draw);

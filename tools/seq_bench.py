@@ -16,6 +16,9 @@ fast_timing. Each step starts from a fresh runtime state (option reset), as benc
                                                         # routes are sm_app_process_device_events here: --route closed
                                                         # with this library, --route nfa with the parent commit's
                                                         # (SM_LIB_VARIANT), which runs the NFA kernel
+    python tools/seq_bench.py --query pattern_streams ...   # the pattern `every e1=A[c1] -> e2=B[c2] within T` on the same
+                                                        # two-way stream index: fast_path 9 (kernels/mpat_dev.h); routes as
+                                                        # for --query streams
 
 Step time is a host clock around work that ends in a device synchronise; a run without a GPU fails."""
 import argparse
@@ -39,13 +42,18 @@ ATTRS = "(symbol int, price double, volume long, timestamp long); "
 SCHEMA_AB = "define stream A " + ATTRS + "define stream B " + ATTRS
 QUERY_AB = ("@info(name='q') from every e1=A[price>20], e2=B[price>e1.price] within 1 sec "
             "select e1.timestamp as i, e2.timestamp as j insert into OutputStream;")
+QUERY_PAT_AB = ("@info(name='q') from every e1=A[price>20] -> e2=B[price>e1.price] within 1 sec "
+                "select e1.timestamp as i, e2.timestamp as j insert into OutputStream;")
 QUERY_ABA = ("@info(name='q') from every e1=A[price>20], e2=B[price>e1.price], e3=A[price>e2.price] within 1 sec "
              "select e1.timestamp as i, e2.timestamp as j, e3.timestamp as l insert into OutputStream;")
 
 
+STREAM_QUERIES = ("streams", "streams3", "pattern_streams")
+
+
 def apps(query):
-    if query in ("streams", "streams3"):
-        q = QUERY_ABA if query == "streams3" else QUERY_AB
+    if query in STREAM_QUERIES:
+        q = {"streams": QUERY_AB, "streams3": QUERY_ABA, "pattern_streams": QUERY_PAT_AB}[query]
         return {"keyed": SCHEMA_AB + "partition with (symbol of A, symbol of B) begin " + q + " end;",
                 "unkeyed": SCHEMA_AB + q}
     q = QUERY3 if query == "three" else QUERY
@@ -57,6 +65,8 @@ LABELS = ["seq_facts", "seq_sort", "seq_link", "seq_keep", "seq_count", "seq_sca
 LABELS += ["seqk_" + l[4:] for l in LABELS]
 LABELS += ["event_index", "mseq_facts", "mseq_pack", "mseq_sort", "mseq_link", "mseq_keep", "mseq_count", "mseq_scan",
            "mseq_emit", "mseq_carry"]
+LABELS += ["mpat_facts", "mpat_pack", "mpat_sort", "mpat_link", "mpat_count", "mpat_scan", "mpat_emit", "mpat_order",
+           "mpat_carry"]
 
 
 def precompile(query):
@@ -64,7 +74,7 @@ def precompile(query):
     into siddhi_amd/jit_cache (the compact lane-event form a 4-attribute stream takes), one process per plan."""
     import subprocess
     procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--query", query, "--precompile-one", form],
-                              env=dict(os.environ, SM_NFA_JIT_COMPACT="1")) for form in APPS]
+                              env=dict(os.environ, SM_NFA_JIT_COMPACT="1")) for form in apps(query)]
     sys.exit(max(p.wait() for p in procs))
 
 
@@ -93,7 +103,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--route", choices=["closed", "nfa"], default="closed")
     ap.add_argument("--forms", default="keyed,unkeyed")
-    ap.add_argument("--query", choices=["pair", "three", "streams", "streams3"], default="pair")
+    ap.add_argument("--query", choices=["pair", "three", "streams", "streams3", "pattern_streams"], default="pair")
     ap.add_argument("--precompile", action="store_true")
     ap.add_argument("--precompile-one")
     a = ap.parse_args()
@@ -113,7 +123,7 @@ def main():
     n = int(a.events)
     sym, price, _, _, ts = bench.gen_stock(0, n, a.keys, a.ts_div, dev, bench.seed_for(4))
     ordinals = torch.arange(n, dtype=torch.int64, device=dev)  # the timestamp attribute = the event's ordinal
-    streams = a.query in ("streams", "streams3")
+    streams = a.query in STREAM_QUERIES
     sidx = torch.zeros(n, dtype=torch.int32, device=dev) if a.route == "nfa" or streams else None
     if streams:  # a deterministic two-way stream index from the row number
         x = ordinals * (0x9E3779B97F4A7C15 - (1 << 64))  # (wraps: a multiply-xorshift hash, one bit of it)
