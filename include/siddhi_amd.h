@@ -333,7 +333,11 @@ int sm_app_device_project(sm_app* app, const char* query_name, sm_dval* d_values
  * `every e1, e2` sequences 6 = adjacent-pair kernels (labels seq_facts, seq_sort, seq_link, seq_keep, seq_count,
  * seq_scan, seq_emit, seq_carry), 5 = general NFA kernel; k-state sequences (3 <= k <= 8) 7 = adjacent-run kernels
  * (labels seqk_facts, seqk_sort, seqk_link, seqk_keep, seqk_count, seqk_scan, seqk_emit, seqk_carry), 5 = general NFA
- * kernel; filter queries 3 = filter interpreter, 4 = typed conjunction. "output_events:<query>" = its output count.
+ * kernel; through sm_app_process_device_events (the label event_index first): sequences over several streams 8 =
+ * adjacent-run kernels on the read rows (labels mseq_facts, mseq_pack, mseq_sort, mseq_link, mseq_keep, mseq_count,
+ * mseq_scan, mseq_emit, mseq_carry), the pattern over two streams 9 (labels mpat_facts, mpat_pack, mpat_sort, mpat_link,
+ * mpat_count, mpat_scan, mpat_emit, mpat_order, mpat_carry), 5 = general NFA kernel;
+ * filter queries 3 = filter interpreter, 4 = typed conjunction. "output_events:<query>" = its output count.
  * "match_arity:<query>" = uint32 words per tuple of sm_app_device_matches: k for a k-state sequence of the adjacent-run
  * form, 2 for every other pattern or sequence, 1 for a filter (its kept row).
  * "kernel_ms:<label>" / "kernel_calls:<label>" and "fast_ms:group" / "fast_ms:walk" / "fast_ms:order" (per-kernel

@@ -44,7 +44,7 @@ struct CompiledQuery {
   // shares fast_within / fast_c1_* / fast_c2_*
   bool fast_seq_adjacent = false;
   // fast path: every e1=S[c1], e2=S[c2], ..., ek=S[ck] with 3 <= k <= 8 (sequence: runs of k adjacent events of a
-  // partition instance, seqkpath.hip). fast_seq_k = k (0: not this form); per element m (0-based) its condition
+  // partition instance, seqpath.hip). fast_seq_k = k (0: not this form); per element m (0-based) its condition
   // program (state context, slots 0..m) and its `within` against the previous element's event (-1 = none; element 0
   // has none). The plan carries k hidden ordinal refs (slot m, index 0) after the visible ones.
   int fast_seq_k = 0;
@@ -52,7 +52,7 @@ struct CompiledQuery {
   int64_t fast_k_within[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
   // fast path: every e1=S1[c1], e2=S2[c2], ..., ek=Sk[ck] with 2 <= k <= 8 over at least two streams of one schema
   // (sequence: runs of k adjacent events of a partition instance among the events of the streams the query reads,
-  // mseqpath.hip). fast_seq_ms = k (0: not this form); per element m its app stream index, its condition program
+  // seqpath.hip). fast_seq_ms = k (0: not this form); per element m its app stream index, its condition program
   // (state context, slots 0..m) and its `within` against the previous element's event (-1 = none; element 0 has
   // none). fast_ms_keycol[s] is the INT / LONG key attribute of app stream s when the query is partitioned (-1: the
   // query does not read s). The plan carries k hidden ordinal refs (slot m, index 0) after the visible ones. Such a

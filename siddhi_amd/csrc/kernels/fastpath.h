@@ -42,7 +42,9 @@ struct FastState {
   int cus = 0;              // compute units of the device
   int sort_wgs_per_cu = 0;  // resident down-sweep workgroups per CU (persistent-chunk grid)
   int walk_wgs_per_cu = 0;  // resident walk workgroups per CU
-  int last_path = 0;        // pipeline of the last batch: 2 = sort / walk, 3 = bucket stack, 6 = adjacent pairs
+  // pipeline of the last batch: 2 = sort / walk, 3 = bucket stack; seqpath.hip: 6 = adjacent pairs, 7 = adjacent runs,
+  // 8 = adjacent runs over several streams, 9 = the pattern over two streams
+  int last_path = 0;
 };
 
 struct FastTimings {          // optional HIP events: [0] start, [1] keyed sort done, [2] walk done, [3] end
@@ -124,16 +126,19 @@ int64_t fast_seq_k(const FastArgs& a, const SeqKPlan& p, const FastHostInfo& hi,
 
 // The same form over several streams of one schema, 2 <= k <= 8, on an interleaved batch (seqpath.hip, mseq_dev.h):
 // `sid` is the stream of every row (device); rows of streams outside p.read and heartbeat rows (-1) are ignored.
-struct MSeqPlan {
-  int k = 0;
-  int stream[8] = {0};             // app stream of element m
-  int off[8] = {0}, len[8] = {0};  // condition program of element m (state context)
-  int64_t within[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+struct MSeqKeys {                  // the rows a query reads and their partition keys (fast_seq_ms and fast_pat_ms)
   uint64_t read = 0;               // bit s: the query reads app stream s
   bool keyed = false;
   const void* kcol[64] = {nullptr};  // keyed: the device key column of read stream s (INT, or LONG when bit s of wide)
   uint64_t wide = 0;
   int64_t remap_span = 0;          // as FastHostInfo::remap_span
+};
+
+struct MSeqPlan : MSeqKeys {
+  int k = 0;
+  int stream[8] = {0};             // app stream of element m
+  int off[8] = {0}, len[8] = {0};  // condition program of element m (state context)
+  int64_t within[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
 };
 
 // a.st: the device descriptor of a read stream (all share the columns); a.key / a.c1_* / a.c2_* / a.within are not
@@ -144,16 +149,11 @@ int64_t fast_seq_ms(const FastArgs& a, const int32_t* sid, const MSeqPlan& p, in
                     FastTimings* tm = nullptr);
 
 // The pattern `every e1=A[c1] -> e2=B[c2] within T` over two streams of one schema on an interleaved batch
-// (seqpath.hip, mpat_dev.h has the rule and the kernels). The fields shared with MSeqPlan mean what they mean there.
-struct MPatPlan {
+// (seqpath.hip, mpat_dev.h has the rule and the kernels).
+struct MPatPlan : MSeqKeys {
   int stream[2] = {0, 0};          // app stream of e1 and of e2
   int off[2] = {0, 0}, len[2] = {0, 0};  // c1 and c2 (state context)
   int64_t within = -1;
-  uint64_t read = 0;
-  bool keyed = false;
-  const void* kcol[64] = {nullptr};
-  uint64_t wide = 0;
-  int64_t remap_span = 0;
 };
 
 // a.st, `sid`, key_remap and FAST_KEY_SPAN as fast_seq_ms; pairs and their conventions as fast_every_within_v2: (e1, e2)
@@ -167,7 +167,7 @@ int64_t fast_pat_ms(const FastArgs& a, const int32_t* sid, const MPatPlan& p, in
 
 // keys[i] = the partition key of row i (the key column of its own stream, as int64), 0 for a row that is not read: the
 // one key column remap_keys takes when an interleaved batch's keys become dense ids
-void mseq_gather_keys(int64_t n, const int32_t* sid, const MSeqPlan& p, int64_t* keys, hipStream_t s);
+void mseq_gather_keys(int64_t n, const int32_t* sid, const MSeqKeys& p, int64_t* keys, hipStream_t s);
 
 // ---- internal: the bucket-stack pipeline (stack.hip), entered by fast_every_within_v2 after key pass 0 ----
 

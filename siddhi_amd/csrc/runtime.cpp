@@ -367,8 +367,9 @@ struct QueryRt {
   bool nfa_mode = false;     // a closed-form query handed to the NFA kernel for good (nfa_device_batch)
   int level = 0;             // chaining depth: 0 reads input streams only, L reads a stream a level L-1 query fills
   int nfa_kernel_used = 0;   // 1 = query-specialised NFA kernel, 2 = interpreter (last batch this query ran on the NFA)
-  int fast_path_used = 0;    // 7 = adjacent runs (k-state sequence), 6 = adjacent pairs (sequence), 5 = NFA kernel, 3 = bucket stack, 2 = onesweep form,
-                             // 1 = general form (last device batch)
+  // last device batch: 9 = pattern over two streams, 8 = adjacent runs over several streams, 7 = adjacent runs (k-state
+  // sequence), 6 = adjacent pairs (sequence), 5 = NFA kernel, 3 = bucket stack, 2 = onesweep form, 1 = general form
+  int fast_path_used = 0;
   // what sm_app_device_project needs of the last closed-form batch: its stream, event times, ordinals, and the
   // carry as it was before the batch (carried e1 rows)
   bool proj_ok = false;
@@ -447,38 +448,14 @@ inline bool closed_form(const CompiledQuery& cq) {
   return cq.fast_every_within || cq.fast_seq_adjacent || cq.fast_seq_k > 0;
 }
 
-// The adjacent-run kernels (seqpath.hip fast_seq_k) evaluate element m's condition over slots 0 .. m, one event each:
-// no timestamp reads, no stream-context loads, index 0 or CURRENT only.
-bool seqk_progs_ok(const CompiledQuery& cq) {
+// The adjacent-run kernels (seqpath.hip: fast_seq_k, fast_seq_ms) and the pattern over two streams (fast_pat_ms: c1 reads
+// slot 0, c2 slots 0 and 1) evaluate element m's condition over slots 0 .. m, one event each: no timestamp reads, no
+// stream-context loads, index 0 or CURRENT only.
+bool run_progs_ok(const CompiledQuery& cq, const int* off, const int* len, int k) {
   const Instr* code = (const Instr*)(cq.blob.data() + cq.hdr.off_code);
-  for (int m = 0; m < cq.fast_seq_k; ++m)
-    for (int k = 0; k < cq.fast_k_len[m]; ++k) {
-      const Instr& in = code[cq.fast_k_off[m] + k];
-      if (in.op == OP_TS || in.op == OP_COL) return false;
-      if (in.op == OP_VAR && (in.a < 0 || in.a > m || !(in.b == 0 || in.b == -1))) return false;
-    }
-  return true;
-}
-
-// The same check for a sequence over several streams (fast_seq_ms: seqpath.hip, mseq_dev.h).
-bool mseq_progs_ok(const CompiledQuery& cq) {
-  const Instr* code = (const Instr*)(cq.blob.data() + cq.hdr.off_code);
-  for (int m = 0; m < cq.fast_seq_ms; ++m)
-    for (int k = 0; k < cq.fast_ms_len[m]; ++k) {
-      const Instr& in = code[cq.fast_ms_off[m] + k];
-      if (in.op == OP_TS || in.op == OP_COL) return false;
-      if (in.op == OP_VAR && (in.a < 0 || in.a > m || !(in.b == 0 || in.b == -1))) return false;
-    }
-  return true;
-}
-
-// The same check for the pattern over two streams (fast_pat_ms: seqpath.hip, mpat_dev.h): c1 reads slot 0, c2 slots 0
-// and 1.
-bool mpat_progs_ok(const CompiledQuery& cq) {
-  const Instr* code = (const Instr*)(cq.blob.data() + cq.hdr.off_code);
-  for (int m = 0; m < 2; ++m)
-    for (int k = 0; k < cq.fast_pat_len[m]; ++k) {
-      const Instr& in = code[cq.fast_pat_off[m] + k];
+  for (int m = 0; m < k; ++m)
+    for (int i = 0; i < len[m]; ++i) {
+      const Instr& in = code[off[m] + i];
       if (in.op == OP_TS || in.op == OP_COL) return false;
       if (in.op == OP_VAR && (in.a < 0 || in.a > m || !(in.b == 0 || in.b == -1))) return false;
     }
@@ -2588,6 +2565,49 @@ void run_chained(sm_app* a, std::vector<HostOut>& outs) {
   outs.swap(sorted);
 }
 
+// One device batch through a query's closed form, with its partition keys as values or as dense ids (any key domain:
+// ValuePartitionExecutor, core/partition/executor/ValuePartitionExecutor.java:34-39, keys by any value, so a sparse
+// 64-bit id must not leave the closed form). Which of the two is decided at the query's first closed-form batch, then
+// kept, since the carried partials hold ids: option "key_remap", or (automatic) ids when the first batch's key span
+// exceeds the bucket-stack window (2^20). That batch runs on the values with *remap_span set, and its facts report a
+// wider span (FAST_KEY_SPAN) before anything changes; then the carried partials' keys become ids too (each key's rows
+// stay one run, so the carry keeps its grouping) and the batch runs again. The carry as it is before the batch stays in
+// prev_carry, for the projection of matches whose first events were carried.
+//   keyed     the batch has rows and a key column that can take ids
+//   dense()   the closed form reads dense ids (remap_keys) instead of the key column from here on
+//   closed()  runs the closed form
+template <class Dense, class Closed>
+int64_t closed_form_batch(sm_app* a, QueryRt& q, bool keyed, int64_t* remap_span, hipStream_t hs, Dense dense,
+                          Closed closed) {
+  if (keyed) {
+    if (q.remap == 0 && !q.carry.active) {
+      if (a->key_remap >= 0) q.remap = a->key_remap ? 1 : 2;
+      else *remap_span = (int64_t)1 << 20;
+    }
+    if (q.remap == 1) dense();
+  }
+  auto snapshot = [&] {
+    if (q.carry.n == 0) return;
+    const size_t cb = (size_t)q.carry.n * q.carry.width * 8;
+    q.prev_carry.ensure(cb);
+    SM_HIP(hipMemcpyAsync(q.prev_carry.p, q.carry.rows, cb, hipMemcpyDeviceToDevice, hs));
+  };
+  q.prev_carry_n = q.carry.n;
+  q.prev_carry_w = q.carry.width;
+  snapshot();
+  int64_t m = closed();
+  if (m == FAST_KEY_SPAN && q.remap != 1 && a->key_remap < 0 && keyed) {
+    q.remap = 1;
+    *remap_span = 0;
+    remap_carry_keys(q.dense, q.carry.rows, q.carry.n, q.carry.width, a->sc, hs);
+    snapshot();
+    dense();
+    m = closed();
+  }
+  if (q.remap == 0 && *remap_span > 0 && m != FAST_OUTSIDE) q.remap = 2;  // the span fitted: values from here on
+  return m;
+}
+
 // The device-batch path of one stream (sm_app_process_device_batch, and host-API batches of apps whose queries all
 // take it: flush_device; large columnar sends: bulk_send_device): every query reading stream s runs over the n
 // events (columns, event times and ordinals in device memory) on hs; the outputs that have consumers are appended to
@@ -2709,36 +2729,14 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
         hi.key_type = types[hi.key_col];
       }
     }
-    // partition keys as dense ids (any key domain): decided at the query's first closed-form batch, then kept, since
-    // the carried partials hold ids; ValuePartitionExecutor (core/partition/executor/ValuePartitionExecutor.java:34-39)
-    // keys by any value, so a sparse 64-bit id must not leave the closed form
-    if (fa.key && hi.key_col >= 0 && (!a->force_general_fast || cq.fast_seq_adjacent || cq.fast_seq_k) && n > 0) {
-      if (q.remap == 0 && !q.carry.active) {
-        // option "key_remap", or (automatic) ids when the first batch's key span exceeds the bucket-stack window
-        // (2^20): the batch runs on the values with remap_span set, and its prep pass reports a wider span
-        // (FAST_KEY_SPAN) before anything changes
-        if (a->key_remap >= 0) q.remap = a->key_remap ? 1 : 2;
-        else hi.remap_span = (int64_t)1 << 20;
-      }
-      if (q.remap == 1) {  // the pipelines read the ids instead of the key column (the column keeps its values)
-        int32_t* dk = (int32_t*)a->sc.take(n * 4);
-        remap_keys(q.dense, hi.cols[hi.key_col], hi.key_type, (int64_t)n, dk, hs);
-        hi.dense_keys = dk;
-      }
-    }
-    q.prev_carry_n = q.carry.n;
-    q.prev_carry_w = q.carry.width;
-    if (q.carry.n > 0) {
-      const size_t cb = (size_t)q.carry.n * q.carry.width * 8;
-      q.prev_carry.ensure(cb);
-      SM_HIP(hipMemcpyAsync(q.prev_carry.p, q.carry.rows, cb, hipMemcpyDeviceToDevice, hs));
-    }
     // the closed form of this query: the pattern's pipelines, the sequence's adjacent-pair kernels (path 6) or, for a
     // k-state sequence, the adjacent-run kernels (path 7)
     const bool seq = cq.fast_seq_adjacent || cq.fast_seq_k;
+    FastTimings* tm = a->fast_timing ? &a->fast_tm : nullptr;
     auto closed = [&]() -> int64_t {
+      if (a->force_general_fast && !seq) return FAST_OUTSIDE;
       if (cq.fast_seq_k) {
-        if (!seqk_progs_ok(cq)) return FAST_OUTSIDE;
+        if (!run_progs_ok(cq, cq.fast_k_off, cq.fast_k_len, cq.fast_seq_k)) return FAST_OUTSIDE;
         SeqKPlan kp;
         kp.k = cq.fast_seq_k;
         for (int m = 0; m < kp.k; ++m) {
@@ -2746,39 +2744,26 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
           kp.len[m] = cq.fast_k_len[m];
           kp.within[m] = cq.fast_k_within[m];
         }
-        return fast_seq_k(fa, kp, hi, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, (int64_t)n, a->sc, hs,
-                          a->fast_timing ? &a->fast_tm : nullptr);
+        return fast_seq_k(fa, kp, hi, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, (int64_t)n, a->sc, hs, tm);
       }
       if (seq)
         return seq_progs_ok(cq) ? fast_seq_adjacent(fa, hi, q.fast, q.carry, (uint32_t*)q.dev_pairs.p,
-                                                    (int64_t)(n + q.carry.n), a->sc, hs,
-                                                    a->fast_timing ? &a->fast_tm : nullptr)
+                                                    (int64_t)(n + q.carry.n), a->sc, hs, tm)
                                 : (int64_t)FAST_OUTSIDE;
       return fast_every_within_v2(fa, hi, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, (int64_t)(n + q.carry.n), a->sc,
-                                  hs, a->fast_timing ? &a->fast_tm : nullptr, a->fast_stack);
+                                  hs, tm, a->fast_stack);
     };
-    int64_t m = FAST_OUTSIDE;
-    if (!a->force_general_fast || seq) m = closed();
-    if (m == FAST_KEY_SPAN && q.remap != 1 && a->key_remap < 0 && fa.key && hi.key_col >= 0) {
-      // the first batch's keys span more than the bucket-stack window, or a later batch's keys leave the span the
-      // first batch showed: dense ids from here on, for the carried partials' keys too (each key's rows stay one
-      // run, so the carry keeps its grouping)
-      q.remap = 1;
-      hi.remap_span = 0;
-      remap_carry_keys(q.dense, q.carry.rows, q.carry.n, q.carry.width, a->sc, hs);
-      if (q.carry.n > 0)
-        SM_HIP(hipMemcpyAsync(q.prev_carry.p, q.carry.rows, (size_t)q.carry.n * q.carry.width * 8,
-                              hipMemcpyDeviceToDevice, hs));
+    auto dense_keys = [&] {  // the pipelines read the ids instead of the key column (the column keeps its values)
       int32_t* dk = (int32_t*)a->sc.take(n * 4);
       remap_keys(q.dense, hi.cols[hi.key_col], hi.key_type, (int64_t)n, dk, hs);
       hi.dense_keys = dk;
-      m = closed();
-    }
-    if (q.remap == 0 && hi.remap_span > 0 && m != FAST_OUTSIDE) q.remap = 2;  // the span fitted: values from here on
+    };
+    const bool keyed = fa.key && hi.key_col >= 0 && (!a->force_general_fast || seq) && n > 0;
+    int64_t m = closed_form_batch(a, q, keyed, &hi.remap_span, hs, dense_keys, closed);
     q.fast_path_used = q.fast.last_path;
     if (m == FAST_OUTSIDE && a->force_general_fast && q.carry.n == 0 && !seq) {
       // diagnostic (option "fast_general"): the stateless general closed form, one batch at a time
-      m = fast_every_within(fa, (uint32_t*)q.dev_pairs.p, (int64_t)n, a->sc, hs, a->fast_timing ? &a->fast_tm : nullptr);
+      m = fast_every_within(fa, (uint32_t*)q.dev_pairs.p, (int64_t)n, a->sc, hs, tm);
       q.fast_path_used = 1;
     } else if (m < 0) {
       // event time not monotone, or a condition outside the v2 envelope: the NFA kernel takes the query over
@@ -2793,17 +2778,20 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
   }
 }
 
-// The closed form of a sequence over several streams of one schema (CompiledQuery::fast_seq_ms; seqpath.hip
-// fast_seq_ms, path 8) over one interleaved device batch (sm_app_process_device_events): `nst` are the host copies of
-// the batch's stream descriptors, already uploaded to d_streams. Returns the number of matches (tuples in dev_pairs,
-// the projection state set as in device_batch_stream; the outputs that have consumers appended to draw), or
-// FAST_OUTSIDE / FAST_NON_MONOTONE with nothing changed.
-int64_t mseq_device_events(sm_app* a, int qi, size_t n, const int32_t* d_stream_idx, const int64_t* d_ts,
-                           const void* const* d_cols, const int64_t* d_ordinals, int64_t ordinal_base,
-                           const std::vector<NfaStream>& nst, hipStream_t hs, std::vector<DevOut>& draw) {
+// The closed forms over one interleaved device batch (sm_app_process_device_events; seqpath.hip): a sequence over
+// several streams of one schema (CompiledQuery::fast_seq_ms, fast_seq_ms, path 8: k-tuples in dev_pairs) or the pattern
+// `every e1=A -> e2=B within T` over two streams (CompiledQuery::fast_pat_ms, fast_pat_ms, path 9: (e1, e2) pairs, an e1
+// carried from an earlier batch projected from prev_carry). `nst` are the host copies of the batch's stream
+// descriptors, already uploaded to d_streams. Returns the number of matches (the projection state set as in
+// device_batch_stream; the outputs that have consumers appended to draw), or FAST_OUTSIDE / FAST_NON_MONOTONE with
+// nothing changed.
+int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_stream_idx, const int64_t* d_ts,
+                                  const void* const* d_cols, const int64_t* d_ordinals, int64_t ordinal_base,
+                                  const std::vector<NfaStream>& nst, hipStream_t hs, std::vector<DevOut>& draw) {
   QueryRt& q = *a->queries[qi];
   const CompiledQuery& cq = q.cq;
-  const int s0 = cq.streams.at(0);
+  const bool pat = cq.fast_pat_ms;
+  const int s0 = pat ? cq.fast_pat_stream[0] : cq.streams.at(0);
   const NfaStream& d = nst[s0];
   const char* blob = (const char*)q.blob.p;
   a->sc.used = 0;
@@ -2813,166 +2801,56 @@ int64_t mseq_device_events(sm_app* a, int qi, size_t n, const int32_t* d_stream_
   fa.st = (const NfaStream*)a->d_streams.p + s0;
   fa.code = (const Instr*)(blob + cq.hdr.off_code);
   fa.consts = (const DVal*)(blob + cq.hdr.off_const);
-  fa.within = -1;
+  fa.within = pat ? cq.fast_pat_within : -1;
   fa.ordinals = d_ordinals;
   fa.ordinal_base = ordinal_base;
-  MSeqPlan mp;
-  mp.k = cq.fast_seq_ms;
-  for (int m = 0; m < mp.k; ++m) {
-    mp.stream[m] = cq.fast_ms_stream[m];
-    mp.off[m] = cq.fast_ms_off[m];
-    mp.len[m] = cq.fast_ms_len[m];
-    mp.within[m] = cq.fast_ms_within[m];
-  }
-  mp.keyed = cq.partition >= 0;
-  auto own_keys = [&] {  // every read stream's own key attribute
-    mp.wide = 0;
-    for (int s : cq.streams) {
-      mp.read |= 1ull << s;
-      if (!mp.keyed) continue;
-      const int c = cq.fast_ms_keycol.at(s);
-      mp.kcol[s] = d_cols[c];
-      if (d.types[c] == T_LONG) mp.wide |= 1ull << s;
+  MSeqPlan sp;
+  MPatPlan pp;
+  std::vector<int> read;  // the streams the query reads
+  if (pat) {
+    for (int m = 0; m < 2; ++m) {
+      pp.stream[m] = cq.fast_pat_stream[m];
+      pp.off[m] = cq.fast_pat_off[m];
+      pp.len[m] = cq.fast_pat_len[m];
     }
-  };
-  own_keys();
+    pp.within = cq.fast_pat_within;
+    read.assign(pp.stream, pp.stream + 2);
+  } else {
+    sp.k = cq.fast_seq_ms;
+    for (int m = 0; m < sp.k; ++m) {
+      sp.stream[m] = cq.fast_ms_stream[m];
+      sp.off[m] = cq.fast_ms_off[m];
+      sp.len[m] = cq.fast_ms_len[m];
+      sp.within[m] = cq.fast_ms_within[m];
+    }
+    read = cq.streams;
+  }
+  MSeqKeys& keys = pat ? static_cast<MSeqKeys&>(pp) : sp;
+  keys.keyed = cq.partition >= 0;
+  for (int s : read) {  // every read stream's own key attribute
+    keys.read |= 1ull << s;
+    if (!keys.keyed) continue;
+    const int c = (pat ? cq.fast_pat_keycol : cq.fast_ms_keycol).at(s);
+    keys.kcol[s] = d_cols[c];
+    if (d.types[c] == T_LONG) keys.wide |= 1ull << s;
+  }
   auto dense_keys = [&] {  // the keys as dense ids (remap_keys), one int32 per row, read instead of the columns
-    int64_t* keys = (int64_t*)a->sc.take(n * 8);
+    int64_t* kv = (int64_t*)a->sc.take(n * 8);
     int32_t* dk = (int32_t*)a->sc.take(n * 4);
-    mseq_gather_keys((int64_t)n, d_stream_idx, mp, keys, hs);
-    remap_keys(q.dense, keys, T_LONG, (int64_t)n, dk, hs);
-    for (int s : cq.streams) mp.kcol[s] = dk;
-    mp.wide = 0;
+    mseq_gather_keys((int64_t)n, d_stream_idx, keys, kv, hs);
+    remap_keys(q.dense, kv, T_LONG, (int64_t)n, dk, hs);
+    for (int s : read) keys.kcol[s] = dk;
+    keys.wide = 0;
   };
-  if (mp.keyed && n > 0) {  // as device_batch_stream: decided at the query's first closed-form batch, then kept
-    if (q.remap == 0 && !q.carry.active) {
-      if (a->key_remap >= 0) q.remap = a->key_remap ? 1 : 2;
-      else mp.remap_span = (int64_t)1 << 20;
-    }
-    if (q.remap == 1) dense_keys();
-  }
-  q.dev_pairs.ensure(std::max<size_t>(n * 4 * (size_t)mp.k, 16));
-  q.prev_carry_n = q.carry.n;
-  q.prev_carry_w = q.carry.width;
-  if (q.carry.n > 0) {
-    const size_t cb = (size_t)q.carry.n * q.carry.width * 8;
-    q.prev_carry.ensure(cb);
-    SM_HIP(hipMemcpyAsync(q.prev_carry.p, q.carry.rows, cb, hipMemcpyDeviceToDevice, hs));
-  }
+  // a sequence: k words per match, at most one match per event; the pattern: (e1, e2) per match, at most one per partial
+  const int64_t cap = pat ? (int64_t)n + q.carry.n : (int64_t)n;
+  q.dev_pairs.ensure(std::max<size_t>(pat ? (size_t)cap * 8 : n * 4 * (size_t)sp.k, 16));
   FastTimings* tm = a->fast_timing ? &a->fast_tm : nullptr;
   auto closed = [&] {
-    return fast_seq_ms(fa, d_stream_idx, mp, d.nattr, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, (int64_t)n, a->sc, hs,
-                       tm);
+    return pat ? fast_pat_ms(fa, d_stream_idx, pp, d.nattr, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, cap, a->sc, hs, tm)
+               : fast_seq_ms(fa, d_stream_idx, sp, d.nattr, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, cap, a->sc, hs, tm);
   };
-  int64_t m = closed();
-  if (m == FAST_KEY_SPAN && q.remap != 1 && a->key_remap < 0 && mp.keyed) {
-    q.remap = 1;
-    mp.remap_span = 0;
-    remap_carry_keys(q.dense, q.carry.rows, q.carry.n, q.carry.width, a->sc, hs);
-    if (q.carry.n > 0)
-      SM_HIP(hipMemcpyAsync(q.prev_carry.p, q.carry.rows, (size_t)q.carry.n * q.carry.width * 8,
-                            hipMemcpyDeviceToDevice, hs));
-    dense_keys();
-    m = closed();
-  }
-  if (q.remap == 0 && mp.remap_span > 0 && m != FAST_OUTSIDE) q.remap = 2;  // the span fitted: values from here on
-  if (m < 0) return m == FAST_NON_MONOTONE ? m : (int64_t)FAST_OUTSIDE;
-  q.fast_path_used = q.fast.last_path;
-  q.proj_nfa = false;
-  q.proj_desc = d;
-  q.proj_ts = d_ts;
-  q.proj_ord = d_ordinals;
-  q.proj_base = ordinal_base;
-  q.proj_n = (int64_t)n;
-  q.dev_n = m;
-  q.proj_ok = true;
-  if (outputs_consumed(a, q)) device_outputs(a, qi, hs, draw);
-  else q.n_out += m;
-  return m;
-}
-
-// The closed form of the pattern `every e1=A -> e2=B within T` over two streams of one schema
-// (CompiledQuery::fast_pat_ms; seqpath.hip fast_pat_ms, path 9) over one interleaved device batch: arguments and
-// results as mseq_device_events. After the match count it is the pattern branch: (e1, e2) pairs in dev_pairs, an e1
-// carried from an earlier batch projected from prev_carry.
-int64_t mpat_device_events(sm_app* a, int qi, size_t n, const int32_t* d_stream_idx, const int64_t* d_ts,
-                           const void* const* d_cols, const int64_t* d_ordinals, int64_t ordinal_base,
-                           const std::vector<NfaStream>& nst, hipStream_t hs, std::vector<DevOut>& draw) {
-  QueryRt& q = *a->queries[qi];
-  const CompiledQuery& cq = q.cq;
-  const int s0 = cq.fast_pat_stream[0];
-  const NfaStream& d = nst[s0];
-  const char* blob = (const char*)q.blob.p;
-  a->sc.used = 0;
-  FastArgs fa{};
-  fa.n = (int64_t)n;
-  fa.ts = d_ts;
-  fa.st = (const NfaStream*)a->d_streams.p + s0;
-  fa.code = (const Instr*)(blob + cq.hdr.off_code);
-  fa.consts = (const DVal*)(blob + cq.hdr.off_const);
-  fa.within = cq.fast_pat_within;
-  fa.ordinals = d_ordinals;
-  fa.ordinal_base = ordinal_base;
-  MPatPlan mp;
-  MSeqPlan kp;  // the key columns, for mseq_gather_keys
-  for (int m = 0; m < 2; ++m) {
-    mp.stream[m] = cq.fast_pat_stream[m];
-    mp.off[m] = cq.fast_pat_off[m];
-    mp.len[m] = cq.fast_pat_len[m];
-    mp.read |= 1ull << cq.fast_pat_stream[m];
-  }
-  mp.within = cq.fast_pat_within;
-  mp.keyed = cq.partition >= 0;
-  if (mp.keyed)
-    for (int m = 0; m < 2; ++m) {  // each stream's own key attribute
-      const int s = mp.stream[m], c = cq.fast_pat_keycol.at(s);
-      mp.kcol[s] = d_cols[c];
-      if (d.types[c] == T_LONG) mp.wide |= 1ull << s;
-    }
-  kp.read = mp.read;
-  kp.keyed = mp.keyed;
-  kp.wide = mp.wide;
-  for (int m = 0; m < 2; ++m) kp.kcol[mp.stream[m]] = mp.kcol[mp.stream[m]];
-  auto dense_keys = [&] {  // the keys as dense ids (remap_keys), one int32 per row, read instead of the columns
-    int64_t* keys = (int64_t*)a->sc.take(n * 8);
-    int32_t* dk = (int32_t*)a->sc.take(n * 4);
-    mseq_gather_keys((int64_t)n, d_stream_idx, kp, keys, hs);
-    remap_keys(q.dense, keys, T_LONG, (int64_t)n, dk, hs);
-    for (int m = 0; m < 2; ++m) mp.kcol[mp.stream[m]] = dk;
-    mp.wide = 0;
-  };
-  if (mp.keyed && n > 0) {  // as mseq_device_events: decided at the query's first closed-form batch, then kept
-    if (q.remap == 0 && !q.carry.active) {
-      if (a->key_remap >= 0) q.remap = a->key_remap ? 1 : 2;
-      else mp.remap_span = (int64_t)1 << 20;
-    }
-    if (q.remap == 1) dense_keys();
-  }
-  const int64_t cap = (int64_t)n + q.carry.n;
-  q.dev_pairs.ensure(std::max<size_t>((size_t)cap * 8, 16));
-  q.prev_carry_n = q.carry.n;
-  q.prev_carry_w = q.carry.width;
-  if (q.carry.n > 0) {
-    const size_t cb = (size_t)q.carry.n * q.carry.width * 8;
-    q.prev_carry.ensure(cb);
-    SM_HIP(hipMemcpyAsync(q.prev_carry.p, q.carry.rows, cb, hipMemcpyDeviceToDevice, hs));
-  }
-  FastTimings* tm = a->fast_timing ? &a->fast_tm : nullptr;
-  auto closed = [&] {
-    return fast_pat_ms(fa, d_stream_idx, mp, d.nattr, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, cap, a->sc, hs, tm);
-  };
-  int64_t m = closed();
-  if (m == FAST_KEY_SPAN && q.remap != 1 && a->key_remap < 0 && mp.keyed) {
-    q.remap = 1;
-    mp.remap_span = 0;
-    remap_carry_keys(q.dense, q.carry.rows, q.carry.n, q.carry.width, a->sc, hs);
-    if (q.carry.n > 0)
-      SM_HIP(hipMemcpyAsync(q.prev_carry.p, q.carry.rows, (size_t)q.carry.n * q.carry.width * 8,
-                            hipMemcpyDeviceToDevice, hs));
-    dense_keys();
-    m = closed();
-  }
-  if (q.remap == 0 && mp.remap_span > 0 && m != FAST_OUTSIDE) q.remap = 2;  // the span fitted: values from here on
+  const int64_t m = closed_form_batch(a, q, keys.keyed && n > 0, &keys.remap_span, hs, dense_keys, closed);
   if (m < 0) return m == FAST_NON_MONOTONE ? m : (int64_t)FAST_OUTSIDE;
   q.fast_path_used = q.fast.last_path;
   q.proj_nfa = false;
@@ -3843,14 +3721,17 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
       QueryRt& q = *msq;
       try {
         const bool pat = q.cq.fast_pat_ms;
-        if (ms_tuples && !q.nfa_mode && !q.nfa_used && (pat ? mpat_progs_ok(q.cq) : mseq_progs_ok(q.cq))) {
+        const CompiledQuery& cq = q.cq;
+        if (ms_tuples && !q.nfa_mode && !q.nfa_used &&
+            (pat ? run_progs_ok(cq, cq.fast_pat_off, cq.fast_pat_len, 2)
+                 : run_progs_ok(cq, cq.fast_ms_off, cq.fast_ms_len, cq.fast_seq_ms))) {
           std::vector<HostOut> douts;
           std::vector<DevOut> draw;
           a->out_arena.clear();
           q.n_out = 0;
           q.ev_out_n = 0;
-          const int64_t m = (pat ? mpat_device_events : mseq_device_events)(a, 0, n, d_stream_idx, d_ts, d_cols, d_ordinals,
-                                                                            ordinal_base, nst, hs, draw);
+          const int64_t m = interleaved_device_events(a, 0, n, d_stream_idx, d_ts, d_cols, d_ordinals, ordinal_base, nst,
+                                                      hs, draw);
           if (m >= 0) {  // the closed form leaves the playback clock alone, as on the device-batch path
             if (!d_ordinals) a->next_ordinal = std::max<int64_t>(a->next_ordinal, ordinal_base + N);
             deliver_device(a, douts, draw);

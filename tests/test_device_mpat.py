@@ -11,7 +11,8 @@ import struct
 import numpy as np
 import pytest
 
-from test_device_mseq import NAMES, Run, events, oracle_out, run, send_rows, straddling, tuples_of
+from test_device_mseq import (NAMES, Run, events, oracle_on_read_rows, oracle_out, run, send_rows, straddling, tuples_of,
+                              unread_rows_going_back)
 
 pytestmark = pytest.mark.gpu
 
@@ -133,6 +134,37 @@ def test_other_direction_and_third_stream_as_e1():
         got, _, paths, _ = run(t, sid, cols, ts, cuts_inside_pairs(exp, len(ts)))
         assert set(paths) == {9}
         np.testing.assert_array_equal(got, exp)
+
+
+@pytest.mark.parametrize("keyed", [True, False])
+def test_unread_rows_going_back_in_time_between_e1_and_e2(keyed):
+    """Three batches: 1025 rows (one more than a tile) of A that leave open partials, 65 rows of C and heartbeats whose
+    event times decrease and lie before the first batch's, and 1025 rows of B, in time order after the first batch, that
+    complete the partials. The batch without a read row neither reports decreasing time nor moves the carried time: every
+    batch stays on the closed form, and the pairs, all of which straddle the middle batch, are the oracle's on the
+    read rows."""
+    n1 = 1025
+    rng = np.random.default_rng(23)
+    a_sid = np.zeros(n1, np.int32)
+    a_sid[::16] = -1
+    step = np.arange(n1, dtype=np.int64) // 16
+    sid = np.concatenate([a_sid, np.ones(n1, np.int32)])
+    sym = rng.integers(0, 5 if keyed else 1, 2 * n1).astype(np.int32)
+    price = np.concatenate([21.0 + np.round(rng.random(n1) * 19.0, 1), 30.0 + np.round(rng.random(n1) * 30.0, 1)])
+    vol = rng.integers(0, 2000, 2 * n1).astype(np.int64)
+    ts = 1000 + np.concatenate([step, step[-1] + step])  # the third batch starts at the first one's last event time
+    sid, cols, ts = unread_rows_going_back(sid, (sym, price, vol), ts, n1)
+    ranges = [(0, n1), (n1, n1 + 65), (n1 + 65, len(ts))]
+    assert (np.diff(ts[n1:n1 + 65]) < 0).all() and ts[n1] < ts[0] and ts[n1 + 65] == ts[n1 - 1]
+    assert not np.isin(sid[n1:n1 + 65], [0, 1]).any()
+    t = text(keys=BY_SYMBOL if keyed else None)  # (T_KEYED: longer than the stream)
+    exp = tuples_of(oracle_on_read_rows(t, sid, cols, ts, [0, 1]), 2)
+    across = straddling(exp, ranges)
+    assert across == len(exp) >= 900  # (960 A rows pass c1; a B row with a higher price follows each inside T)
+    got, _, paths, state = run(t, sid, cols, ts, ranges)
+    assert paths == [9, 9, 9] and state == 0
+    np.testing.assert_array_equal(got, exp)
+    assert straddling(got, ranges) >= across
 
 
 # ---- 3. keys and ordinals

@@ -216,6 +216,52 @@ def test_batches_without_and_with_few_read_rows(keyed):
     np.testing.assert_array_equal(got, exp)
 
 
+def unread_rows_going_back(sid, cols, ts, at, m=65):
+    """The stream with m rows of stream C (which the callers' queries do not read) and heartbeats in front of row `at`:
+    their event times decrease and lie before the stream's first. The timestamp attribute stays the row's position."""
+    assert ts.min() > m
+    usid = np.full(m, 2, np.int32)
+    usid[::4] = -1
+    uts = ts.min() - 1 - np.arange(m, dtype=np.int64)
+    ins = lambda a, b: np.concatenate([a[:at], b.astype(a.dtype), a[at:]])
+    sid = ins(sid, usid)
+    cols = tuple(ins(c, c[:m]) for c in cols[:3]) + (np.arange(len(sid), dtype=np.int64),)
+    return sid, cols, ins(ts, uts)
+
+
+def oracle_on_read_rows(app_text, sid, cols, ts, read):
+    """The oracle fed the rows of the streams `read` alone, each with its position in the whole stream as its ordinal."""
+    rows = np.nonzero(np.isin(sid, read))[0]
+    return oracle_out(app_text, sid[rows], [c[rows] for c in cols], ts[rows], rows.astype(np.int64))
+
+
+@pytest.mark.parametrize("keyed", [True, False])
+@pytest.mark.parametrize("k", [2, 3])
+def test_unread_rows_going_back_in_time_between_members(k, keyed):
+    """Three batches under a `within`: 1025 rows (one more than a tile), 65 rows that the query does not read, whose
+    event times decrease and lie before the first batch's, and 1025 rows. The batch without a read row neither reports
+    decreasing time nor moves the carried time: the third batch stays on the closed form, and tuples whose members lie
+    on both sides of the middle batch come out as the oracle's on the read rows."""
+    pattern = CHAINS[k]
+    sid, cols, ts = events(n=2050, K=5 if keyed else 1, pattern=tuple(pattern), heartbeats=0.05)
+    sid, sym, price, vol = sid.copy(), cols[0].copy(), cols[1].copy(), cols[2].copy()
+    at = np.arange(1026 - k, 1026)  # one key's run of k rows on the pattern's streams, its last row behind the cut
+    sid[at], sym[at], price[at], vol[at] = [NAMES.index(s) for s in pattern], sym[1025], 30.0, 5001 + np.arange(k)
+    sid, cols, ts = unread_rows_going_back(sid, (sym, price, vol), ts + 1000, 1025)
+    ranges = [(0, 1025), (1025, 1090), (1090, len(ts))]
+    assert (np.diff(ts[1025:1090]) < 0).all() and ts[1025] < ts[0] and ts[1090] >= ts[1024]
+    assert not np.isin(sid[1025:1090], [0, 1]).any()
+    t = text(pattern, by_symbol(pattern) if keyed else None, {k: 40})
+    exp = tuples_of(oracle_on_read_rows(t, sid, cols, ts, [0, 1]), k)
+    across = straddling(exp, ranges)
+    assert at[:-1].tolist() + [1090] in exp.tolist()
+    assert across >= 1 and ((exp[:, 0] < 1025) & (exp[:, -1] >= 1090)).sum() == across
+    got, _, paths, state = run(t, sid, cols, ts, ranges)
+    assert paths == [8, 8, 8] and state == 0
+    np.testing.assert_array_equal(got, exp)
+    assert straddling(got, ranges) >= across
+
+
 # ---- 4. tile edges, silent keys
 
 def test_runs_cross_tile_edges_and_a_key_skips_a_batch():
