@@ -53,11 +53,15 @@ __device__ __forceinline__ void wave_lockstep() {
 }
 
 // gfx950 bit / dot instructions, with plain restatements for the host wave emulator
-__device__ __forceinline__ uint32_t sm_sbfe1(uint32_t d, int b) {  // bit b of d as 0 or ~0
+// (stated as the instruction: from the builtin the compiler makes a shift left and a shift right per bit)
+template <int B>
+__device__ __forceinline__ uint32_t sm_sbfe1(uint32_t d) {  // bit B of d as 0 or ~0
 #if defined(__HIP_DEVICE_COMPILE__)
-  return (uint32_t)__builtin_amdgcn_sbfe((int)d, b, 1);
+  uint32_t r;
+  asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(r) : "v"(d), "n"(B));
+  return r;
 #else
-  return ((d >> b) & 1u) ? 0xffffffffu : 0u;
+  return ((d >> B) & 1u) ? 0xffffffffu : 0u;
 #endif
 }
 __device__ __forceinline__ uint32_t sm_and_not_xor(uint32_t a, uint32_t b, uint32_t c) {  // a & ~(b ^ c)
@@ -79,16 +83,18 @@ __device__ __forceinline__ uint32_t sm_udot4(uint32_t a, uint32_t b, uint32_t c)
 
 // Lanes of this wave whose kRB-bit digit equals this lane's (valid lanes only): one ballot per bit, and per
 // bit one v_bitop3 per half, peers &= bit ? ballot : ~ballot  ==  peers & ~(ballot ^ sext(bit)).
+template <int BB>
+__device__ __forceinline__ void peer_mask_bit(uint32_t d, uint32_t& lo, uint32_t& hi) {
+  const uint32_t m = sm_sbfe1<BB>(d);  // 0 or ~0
+  const uint64_t bal = __ballot(m != 0u);
+  lo = sm_and_not_xor(lo, (uint32_t)bal, m);
+  hi = sm_and_not_xor(hi, (uint32_t)(bal >> 32), m);
+  if constexpr (BB + 1 < kRB) peer_mask_bit<BB + 1>(d, lo, hi);
+}
 __device__ __forceinline__ uint64_t peer_mask(uint32_t d, bool valid) {
   const uint64_t v = __ballot(valid);
   uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
-#pragma unroll
-  for (int bb = 0; bb < kRB; ++bb) {
-    const uint32_t m = sm_sbfe1(d, bb);  // 0 or ~0
-    const uint64_t bal = __ballot(m != 0u);
-    lo = sm_and_not_xor(lo, (uint32_t)bal, m);
-    hi = sm_and_not_xor(hi, (uint32_t)(bal >> 32), m);
-  }
+  peer_mask_bit<0>(d, lo, hi);
   return (uint64_t)lo | ((uint64_t)hi << 32);
 }
 
@@ -161,21 +167,35 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
 }
 
 // Block-wide exclusive scan of one value per thread (NT threads, a multiple of 64, at most 1024; the default is the
-// workgroup of the order kernels); returns the total through *tot. lw: NT / 64 words of LDS. One barrier inside,
-// between the write of lw and its reads: the caller fences lw's reuse (a barrier between two scans on the same lw).
-// The wave totals are scanned by every wave alike, in one 16-lane row (lane l holds wave l & 15).
+// workgroup of the order kernels) in two halves, for a caller that has other work to put between them and owns the
+// barrier: block_excl_waves scans within the wave and stores the wave's total to lw[wave] (NT / 64 words of LDS; it
+// returns the lane's inclusive value, which the caller keeps); after a workgroup barrier block_excl_finish scans the
+// wave totals, by every wave alike, in one 16-lane row (lane l holds wave l & 15), and returns the exclusive value and
+// the total through *tot. The caller also fences lw's reuse (a barrier between the finish and the next scan on lw).
 template <int NT = 1024>
-__device__ __forceinline__ uint32_t block_excl(uint32_t v, uint32_t* lw, uint32_t* tot) {
+__device__ __forceinline__ uint32_t block_excl_waves(uint32_t v, uint32_t* lw) {
   static_assert(NT % 64 == 0 && NT / 64 >= 1 && NT / 64 <= 16, "the wave totals fit one 16-lane row");
   const int lane = threadIdx.x & 63, w = wave_index();
   const uint32_t inc = wave_incl_scan(v);
   if (lane == 63) lw[w] = inc;
-  lds_barrier();
+  return inc;
+}
+template <int NT = 1024>
+__device__ __forceinline__ uint32_t block_excl_finish(uint32_t v, uint32_t inc, const uint32_t* lw, uint32_t* tot) {
+  const int lane = threadIdx.x & 63, w = wave_index();
   const int q = lane & 15;
   const uint32_t ws = row_incl_scan(q < NT / 64 ? lw[q] : 0u);
   const uint32_t before = wave_read_lane(ws, w > 0 ? w - 1 : 0);
   *tot = wave_read_lane(ws, NT / 64 - 1);
   return inc - v + (w > 0 ? before : 0u);
+}
+
+// The two halves with their barrier between them: one barrier inside, between the write of lw and its reads.
+template <int NT = 1024>
+__device__ __forceinline__ uint32_t block_excl(uint32_t v, uint32_t* lw, uint32_t* tot) {
+  const uint32_t inc = block_excl_waves<NT>(v, lw);
+  lds_barrier();
+  return block_excl_finish<NT>(v, inc, lw, tot);
 }
 
 __device__ __forceinline__ StackVal col_value(const NfaStream* st, int a, int64_t row) {

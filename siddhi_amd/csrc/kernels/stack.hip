@@ -999,14 +999,17 @@ int64_t stack_pipeline(const StackPlan& p, const FastArgs& a, const FastHostInfo
     }
     tmark("stack");
     if (sa.stamps && !v2) {
-      unsigned long long hst[5];
+      unsigned long long hst[kStamps4];
       SM_HIP(hipMemcpyAsync(hst, sa.stamps, sizeof(hst), hipMemcpyDeviceToHost, s));
       SM_HIP(hipStreamSynchronize(s));
       double tot = 0;
       for (double v : hst) tot += v;
       if (tot > 0)
-        fprintf(stderr, "[stack4 phases] rank %.3f stacks %.3f wait %.3f emit %.3f rest %.3f; wave-clocks %.3g\n",
-                hst[0] / tot, hst[1] / tot, hst[2] / tot, hst[3] / tot, hst[4] / tot, tot);
+        fprintf(stderr,
+                "[stack4 phases] rank0 %.3f stacks %.3f wait %.3f rest %.3f F1 %.3f F2 %.3f F3 %.3f F4 %.3f F5 %.3f "
+                "next %.3f; wave-clocks %.3g\n",
+                hst[0] / tot, hst[1] / tot, hst[2] / tot, (hst[3] + hst[4]) / tot, hst[5] / tot, hst[6] / tot,
+                hst[7] / tot, hst[8] / tot, hst[9] / tot, hst[10] / tot, tot);
     } else if (sa.stamps) {
       unsigned long long hst[7], hcn[2];
       SM_HIP(hipMemcpyAsync(hst, sa.stamps, sizeof(hst), hipMemcpyDeviceToHost, s));

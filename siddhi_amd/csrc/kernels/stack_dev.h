@@ -213,15 +213,15 @@ static_assert(kSS % kT4 == 0 && kI4 * 64 <= 255 && kW4 == 16, "u8 per-(key, wave
 static_assert(kSS <= 32768, "arrival positions | c1 fit 16 bits");
 
 struct Slot4 {
-  uint2 grp[kSS];       // key-grouped records {code, ts - ts0}
+  uint2 grp[kSS];       // key-grouped records {code, ts - ts0}; while the slot is ranked: u8 counts [key][wave]
   uint32_t ordt[kSS];   // ordinal by arrival position
-  uint32_t pk[kSS];     // youngest pop (e1 ordinal) by arrival position    } the ranking's u8 counts [key][wave]
-  uint2 pool[kPool];    // further pops {e1 ordinal, position | k << 16}    } alias pk + pool (16 KB)
+  uint32_t pk[kSS];     // youngest pop (e1 ordinal) by arrival position
+  uint2 pool[kPool];    // further pops {e1 ordinal, position | k << 16}
   uint32_t kst[kKeys];  // run of key h: start | count << 16
   uint16_t epos[kSS];   // key-grouped arrival position | c1 << 15; after the slice's epoch: output offset by position
   uint8_t jc[kSS];      // pops by arrival position
 };
-static_assert(sizeof(uint32_t) * kSS + sizeof(uint2) * kPool >= kKeys * kW4, "ranking counts fit pk + pool");
+static_assert(sizeof(uint2) * kSS >= kKeys * kW4, "ranking counts fit grp");
 
 // fields the event loop does not read (exact comparisons of equal codes, carried partials, carry-out): one struct in
 // device memory, read where needed, so that they hold no registers across the loop
@@ -269,8 +269,13 @@ struct Stack4Args {
 #define SM_STACK4_FLAT 1  // A/B build flag: 0 = every event takes the general (cold) step of the event loop
 #endif
 #ifndef SM_STACK4_STAMPS
-#define SM_STACK4_STAMPS 0  // diagnostic build flag: phase clock of stack4_kernel (0 rank, 1 stacks, 2 wait, 3 emit, 4 rest)
+#define SM_STACK4_STAMPS 0  // diagnostic build flag: phase clock of stack4_kernel; the default build executes no stamp
 #endif
+// Slots of the phase clock: 0 ranking of the first kR slices, 1 event loop, 2 wait at the event loop's barrier (B0),
+// 3 unused (it was the emission), 4 rest, 5 .. 9 the intervals F1 .. F5 of the epoch's chain (chain4), each read
+// before the barrier that ends it, so that the wait at a barrier counts with the interval after it, 10 from before B5
+// to the next event loop (B5's wait, the key runs, the next slice's loads).
+constexpr int kStamps4 = 11;
 #if SM_STACK4_STAMPS && defined(__HIP_DEVICE_COMPILE__)
 #define SM4_CLOCK() __builtin_amdgcn_s_memtime()
 #else
@@ -319,51 +324,159 @@ __device__ __forceinline__ void sm4_arrived(uint4 (&pre)[kI4]) {
 #ifndef SM_RANK4_INLINE
 #define SM_RANK4_INLINE __forceinline__
 #endif
-// rank slice [q0, q0 + sn) of the bucket (records in pre[]) into slot S: key runs (kst), key-grouped {code, ts}
-// and arrival positions | c1, ordinals by arrival position
-__device__ SM_RANK4_INLINE void rank4(Slot4& S, const uint4 (&pre)[kI4], int sn, uint32_t* lw, bool fp,
-                                       uint32_t* err) {
+// what the emission half of an epoch works on besides the slot (chain4)
+struct Emit4 {
+  uint64_t* stb;      // the bucket's staged matches
+  uint32_t* mst;      // the bucket's per-tile staging offsets
+  uint32_t* s_pool;   // the slot's pool count
+  uint32_t* s_lastj;  // ordinal of the previous slice's last record
+  uint32_t* s_tot;
+  uint32_t* lw;       // wave totals of the emission's scan
+  int sn;             // records of the emitted slice
+};
+
+// One epoch's work between two event loops, on slot S, as one chain of five workgroup barriers B1 .. B5 after the
+// caller's barrier B0 (every lane has left the events of the slice S holds). Two halves share every interval:
+//   emission (EMIT): the matches of the slice S holds go to the bucket's staging run, in arrival order of j (count
+//     per event, block scan, placement at (offset of j) + (rank among j's pops counted from the oldest)); it reads
+//     the slot's jc / pk / pool / ordt and writes epos (output offsets by arrival position) and device memory;
+//   ranking (rank): the slice in pre[] (rn records) is ranked by key into S (wave64 ballot peer masks: stable, arrival
+//     order within a key): key runs (kst), key-grouped {code, ts} and arrival positions | c1, ordinals by arrival
+//     position. Its u8 counts [key][wave] lie on S.grp, dead since B0, and it writes the slot's grp / epos / ordt only
+//     in the last interval, so each thread takes what it needs from the counts (the records of earlier waves, `bef`)
+//     one interval before any thread places.
+// Both conditions are block-uniform, so every path executes the same barriers. Intervals:
+//   F1  emission: jc sums, wave scan -> E.lw             ranking: zero the thread's count row
+//   F2  emission: offsets, epos, mst, youngest pops      ranking: count loop
+//   F3  emission: pool pops, mrun                        ranking: key totals, bef, wave scan -> lwR
+//   F4  emission: s_lastj, pool count                    ranking: key starts -> kst
+//   F5                                                   ranking: placement into grp / epos / ordt
+// ordt and epos of the slot are read by F2 .. F4 and overwritten in F5; pk / pool are read in F2 / F3 and next written
+// by the event loop; each lw has a barrier between its last read and its next write.
+// Within an interval a thread's LDS reads are stated together and under no condition (a position past the slice's end
+// reads inside the slot and its value is dropped): a read under `p < sn` or `if (v[k])` is an exec region with a wait
+// of its own, one LDS round trip after the other per record, with four waves per SIMD to cover them.
+// PH: first slot of the phase clock for the five intervals (SM_STACK4_STAMPS builds); < 0: the caller's own.
+template <bool EMIT, int PH>
+__device__ SM_RANK4_INLINE void chain4(Slot4& S, const uint4 (&pre)[kI4], bool rank, int rn, uint32_t* lwR, bool fp,
+                                       uint32_t* err, const Emit4& E, uint32_t& mrun,
+                                       unsigned long long (&st_acc)[kStamps4], unsigned long long& st_last) {
   const int tid = threadIdx.x, lane = tid & 63, w = wave_index();
-  uint8_t* cnt = (uint8_t*)S.pk;  // [key][wave]
-  {
+  uint8_t* cnt = (uint8_t*)S.grp;  // [key][wave]
+  // ---- F1
+  uint32_t v[kI4], sum = 0, incE = 0;
+  if (EMIT) {
+#pragma unroll
+    for (int k = 0; k < kI4; ++k) {
+      const int p = tid * kI4 + k;
+      const uint32_t c = S.jc[p];  // (read under no condition: inside the slot, and the reads go out together)
+      v[k] = p < E.sn ? c : 0u;
+      sum += v[k];
+    }
+    incE = block_excl_waves<kT4>(sum, E.lw);
+  }
+  if (rank) {
     const uint32_t z = sm4_opaque(0u);  // (a zero made here, not one kept in four registers across the kernel)
     *(uint4*)(cnt + 16 * tid) = make_uint4(z, z, z, z);
   }
-  lds_barrier();
-  uint32_t hk[kI4], lp[kI4];
-  bool nan = false;
+  if (PH >= 0) SM4_PHASE(PH);
+  lds_barrier();  // B1
+  // ---- F2
+  if (EMIT) {
+    uint32_t tot;
+    uint32_t r = block_excl_finish<kT4>(sum, incE, E.lw, &tot);
+    // the thread's ordinals and youngest pops, and the ordinal of the record before its first (0xffffffff: the bucket
+    // starts here), in one batch of LDS reads with one wait, not a read and a wait per record under its condition
+    // (the positions at and after sn are inside the slot and never used)
+    uint32_t jo[kI4], yo[kI4];
 #pragma unroll
-  for (int k = 0; k < kI4; ++k) {
-    const int e = w * 64 * kI4 + k * 64 + lane;
-    const bool valid = e < sn;
-    nan |= fp && valid && pre[k].z == kNanCode;  // a NaN sends the batch to the sort / walk kernels (SE_NAN)
-    hk[k] = valid ? (pre[k].x & kKeyMask) >> kRB : 0u;
-    const uint64_t peers = peer_mask(hk[k], valid);
-    uint32_t old = 0;
-    if (valid) old = cnt[16 * hk[k] + w];
-    wave_lockstep();
-    const uint32_t below = lanes_below(peers);
-    if (valid && below == 0) cnt[16 * hk[k] + w] = (uint8_t)(old + (uint32_t)__popcll(peers));
-    wave_lockstep();
-    lp[k] = old + below;
-  }
-  if (__any(nan) && lane == 0) atomicOr(err, SE_NAN);
-  lds_barrier();
-  {  // key h = tid: its count over the waves, block scan over keys
-    const uint4 c = *(const uint4*)(cnt + 16 * tid);
-    const uint32_t ones = 0x01010101u;
-    const uint32_t tot = sm_udot4(c.x, ones, 0u) + sm_udot4(c.y, ones, 0u) +
-                         sm_udot4(c.z, ones, 0u) + sm_udot4(c.w, ones, 0u);
-    uint32_t all;
-    const uint32_t st = block_excl<kT4>(tot, lw, &all);
-    S.kst[tid] = st | (tot << 16);
-  }
-  lds_barrier();
+    for (int k = 0; k < kI4; ++k) {
+      jo[k] = S.ordt[tid * kI4 + k];
+      yo[k] = S.pk[tid * kI4 + k];
+    }
+    uint32_t jp = tid == 0 ? *E.s_lastj : S.ordt[tid * kI4 - 1];
 #pragma unroll
-  for (int k = 0; k < kI4; ++k) {
-    const int e = w * 64 * kI4 + k * 64 + lane;
-    if (e < sn) {
-      // same-key records of earlier waves: the bytes of waves 0 .. w-1 in the key's 16-byte row
+    for (int k = 0; k < kI4; ++k) {
+      const int p = tid * kI4 + k;
+      if (p < E.sn) {
+        S.epos[p] = (uint16_t)r;  // the key-grouped positions are dead: output offsets by arrival position
+        const uint32_t j = jo[k];
+        // ordinal tiles whose first ordinal falls in (previous record's ordinal, this record's]: their first
+        // match in this bucket is this record's first. From tile (jp >> kTB) + 1, which (jp + kOT) >> kTB also
+        // is where the bucket starts (ordinals are below 2^31; 0xffffffff + kOT wraps to kOT - 1: tile 0)
+        const uint32_t t0 = (jp + (uint32_t)kOT) >> kTB;
+#pragma unroll 1
+        for (uint32_t t = t0; t <= (j >> kTB); ++t) E.mst[t] = mrun + r;
+        jp = j;
+        if (v[k]) E.stb[mrun + r + v[k] - 1u] = ((uint64_t)j << 32) | yo[k];
+      }
+      r += v[k];
+    }
+    if (tid == 0) *E.s_tot = tot;
+  }
+  uint32_t hk[kI4], bef[kI4];  // the record's key; its rank among the key's records of the slice
+  if (rank) {
+    bool nan = false;
+#pragma unroll
+    for (int k = 0; k < kI4; ++k) {
+      const int e = w * 64 * kI4 + k * 64 + lane;
+      const bool valid = e < rn;
+      nan |= fp && valid && pre[k].z == kNanCode;  // a NaN sends the batch to the sort / walk kernels (SE_NAN)
+      hk[k] = valid ? (pre[k].x & kKeyMask) >> kRB : 0u;
+      const uint64_t peers = peer_mask(hk[k], valid);
+      uint32_t old = 0;
+      if (valid) old = cnt[16 * hk[k] + w];
+      wave_lockstep();
+      const uint32_t below = lanes_below(peers);
+      if (valid && below == 0) cnt[16 * hk[k] + w] = (uint8_t)(old + (uint32_t)__popcll(peers));
+      wave_lockstep();
+      bef[k] = old + below;
+    }
+    if (__any(nan) && lane == 0) atomicOr(err, SE_NAN);
+  }
+  if (PH >= 0) SM4_PHASE(PH + 1);
+  lds_barrier();  // B2
+  // ---- F3
+  if (EMIT) {
+    // the thread's pool entries (kPI at most), then what each points at, then the stores: two batches of LDS reads and
+    // not a chain per entry (an entry past the count reads position 0 and stores nothing)
+    constexpr int kPI = (kPool + kT4 - 1) / kT4;
+    const uint32_t np = *E.s_pool < (uint32_t)kPool ? *E.s_pool : (uint32_t)kPool;
+    const uint32_t k0 = sm4_opaque((uint32_t)tid);
+    uint2 pe[kPI];
+#pragma unroll
+    for (int u = 0; u < kPI; ++u) pe[u] = S.pool[k0 + u * kT4 < np ? k0 + u * kT4 : 0u];
+    uint32_t po[kPI], pj[kPI];
+#pragma unroll
+    for (int u = 0; u < kPI; ++u) {
+      const uint32_t p = k0 + u * kT4 < np ? pe[u].y & 0xffffu : 0u;
+      po[u] = S.epos[p] + S.jc[p];
+      pj[u] = S.ordt[p];
+    }
+#pragma unroll
+    for (int u = 0; u < kPI; ++u) {
+      const uint32_t kk = pe[u].y >> 16;
+#ifdef SM_EMU_DEBUG
+      if (k0 + u * kT4 < np && ((pe[u].y & 0xffffu) >= (uint32_t)E.sn || kk >= S.jc[pe[u].y & 0xffffu])) {
+        printf("bad pool entry k=%u/%u p=%u kk=%u sn=%d\n", k0 + u * kT4, np, pe[u].y & 0xffffu, kk, E.sn);
+        continue;
+      }
+#endif
+      if (k0 + u * kT4 < np) E.stb[mrun + po[u] - 1u - kk] = ((uint64_t)pj[u] << 32) | pe[u].x;
+    }
+    mrun += *E.s_tot;
+  }
+  uint32_t tot = 0, incR = 0;
+  if (rank) {
+    {  // key h = tid: its count over the waves
+      const uint4 c = *(const uint4*)(cnt + 16 * tid);
+      const uint32_t ones = 0x01010101u;
+      tot = sm_udot4(c.x, ones, 0u) + sm_udot4(c.y, ones, 0u) + sm_udot4(c.z, ones, 0u) + sm_udot4(c.w, ones, 0u);
+    }
+#pragma unroll
+    for (int k = 0; k < kI4; ++k) {
+      // same-key records of earlier waves: the bytes of waves 0 .. w-1 in the key's 16-byte row (a record past the
+      // slice's end reads row 0 and is not placed: the reads go out together, under no condition)
       const uint4 c = *(const uint4*)(cnt + 16 * hk[k]);
       const uint32_t wb = (uint32_t)w * 8u;  // bits of the row below wave w
       auto part = [&](uint32_t word, uint32_t lo) {
@@ -371,15 +484,43 @@ __device__ SM_RANK4_INLINE void rank4(Slot4& S, const uint4 (&pre)[kI4], int sn,
         const uint32_t m = nb >= 32u ? 0xffffffffu : ((1u << nb) - 1u);
         return sm_udot4(word & m, 0x01010101u, 0u);
       };
-      const uint32_t before = part(c.x, 0) + part(c.y, 32) + part(c.z, 64) + part(c.w, 96);
-      const uint32_t pos = (S.kst[hk[k]] & 0xffffu) + before + lp[k];
-      S.grp[pos] = make_uint2(pre[k].z, pre[k].w);
-      S.epos[pos] = (uint16_t)((uint32_t)e | ((pre[k].x >> 31) << 15));
-      S.ordt[e] = pre[k].y;
-      if (SM_STACK4_SKIP) S.jc[e] = 0;
+      bef[k] += part(c.x, 0) + part(c.y, 32) + part(c.z, 64) + part(c.w, 96);
+    }
+    incR = block_excl_waves<kT4>(tot, lwR);  // block scan over keys
+  }
+  if (PH >= 0) SM4_PHASE(PH + 2);
+  lds_barrier();  // B3
+  // ---- F4
+  if (rank) {
+    uint32_t all;
+    const uint32_t st = block_excl_finish<kT4>(tot, incR, lwR, &all);
+    S.kst[tid] = st | (tot << 16);
+  }
+  if (EMIT && tid == 0) {
+    *E.s_lastj = S.ordt[E.sn - 1];
+    *E.s_pool = 0;
+  }
+  if (PH >= 0) SM4_PHASE(PH + 3);
+  lds_barrier();  // B4
+  // ---- F5
+  if (rank) {
+    uint32_t ks[kI4];
+#pragma unroll
+    for (int k = 0; k < kI4; ++k) ks[k] = S.kst[hk[k]];  // (key 0's for a record past the slice's end)
+#pragma unroll
+    for (int k = 0; k < kI4; ++k) {
+      const int e = w * 64 * kI4 + k * 64 + lane;
+      if (e < rn) {
+        const uint32_t pos = (ks[k] & 0xffffu) + bef[k];
+        S.grp[pos] = make_uint2(pre[k].z, pre[k].w);
+        S.epos[pos] = (uint16_t)((uint32_t)e | ((pre[k].x >> 31) << 15));
+        S.ordt[e] = pre[k].y;
+        if (SM_STACK4_SKIP) S.jc[e] = 0;
+      }
     }
   }
-  lds_barrier();
+  if (PH >= 0) SM4_PHASE(PH + 4);
+  lds_barrier();  // B5
 }
 
 #ifdef SM_HOST_EMU
@@ -413,7 +554,7 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
   const int32_t within32 = a.within;
   const int32_t weff = within32 < 0 ? INT32_MAX : within32;  // no `within`: no difference of two times exceeds it
   uint4* sp = a.spill + ((int64_t)blockIdx.x * kKeys + h) * kQ;
-  unsigned long long st_acc[5] = {0, 0, 0, 0, 0}, st_last = SM4_CLOCK();
+  unsigned long long st_acc[kStamps4] = {}, st_last = SM4_CLOCK();
 
   for (int d = blockIdx.x; d < kBins; d += gridDim.x) {
     const uint32_t b0 = a.dbase[d];
@@ -465,7 +606,7 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
       off[s] = cnt[s] = 0;
       if (s < nsl) {
         load(s);
-        rank4(sl[s], pre, slice_n(s), lw, FP, a.err);
+        chain4<false, -1>(sl[s], pre, true, slice_n(s), lw, FP, a.err, Emit4{}, mrun, st_acc, st_last);
         const uint32_t v = sl[s].kst[h];
         off[s] = v & 0xffffu;
         cnt[s] = v >> 16;
@@ -529,7 +670,7 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
         const int32_t jt = (int32_t)g.y;
         tl = act ? jt : tl;
         seen |= act;
-        // a NaN anywhere sent the batch to the sort / walk kernels (rank4: SE_NAN), so the codes alone decide here.
+        // a NaN anywhere sent the batch to the sort / walk kernels (chain4: SE_NAN), so the codes alone decide here.
         //
         // Straight-line step. The register stack is padded (st_pad) and, for the four ordered compares, monotone: from
         // the top the codes never get easier to beat and the times never get younger (events of a key arrive in time
@@ -738,60 +879,16 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
       lds_barrier();  // every lane is done with slice e
       SM4_PHASE(2);
       sm4_arrived(pre);  // slice e + kR, loaded during the epoch before (unconditional: a wait under a condition
-                         // leaves the compiler its own wait at rank4's first use, behind the stores)
+                         // leaves the compiler its own wait at the ranking's first use, behind the stores)
 
-      // ---- slice e's matches, in arrival order of j
-      {
-        Slot4& S = sl[q0];
-        const int sn = slice_n(e);
-        uint32_t v[kI4], sum = 0;
+#ifdef SM_HOST_EMU
+      {  // emulator build only: nothing reads the slot's key-grouped records after this barrier
 #pragma unroll
-        for (int k = 0; k < kI4; ++k) {
-          const int p = tid * kI4 + k;
-          v[k] = p < sn ? S.jc[p] : 0u;
-          sum += v[k];
-        }
-        uint32_t tot;
-        uint32_t r = block_excl<kT4>(sum, lw, &tot);
-        const uint32_t jprev = s_lastj;
-#pragma unroll
-        for (int k = 0; k < kI4; ++k) {
-          const int p = tid * kI4 + k;
-          if (p < sn) {
-            S.epos[p] = (uint16_t)r;  // the key-grouped positions are dead: output offsets by arrival position
-            const uint32_t j = S.ordt[p];
-            // ordinal tiles whose first ordinal falls in (previous record's ordinal, this record's]: their first
-            // match in this bucket is this record's first
-            const uint32_t jp = p == 0 ? jprev : S.ordt[p - 1];
-            const uint32_t t0 = jp == 0xffffffffu ? 0u : (jp >> kTB) + 1u;
-            for (uint32_t t = t0; t <= (j >> kTB); ++t) mst[t] = mrun + r;
-            if (v[k]) stb[mrun + r + v[k] - 1u] = ((uint64_t)j << 32) | S.pk[p];
-          }
-          r += v[k];
-        }
-        if (tid == 0) s_tot = tot;
-        lds_barrier();
-        const uint32_t np = s_pool[q0] < (uint32_t)kPool ? s_pool[q0] : (uint32_t)kPool;
-        for (uint32_t k = sm4_opaque((uint32_t)tid); k < np; k += kT4) {
-          const uint2 pe = S.pool[k];
-          const uint32_t p = pe.y & 0xffffu, kk = pe.y >> 16;
-#ifdef SM_EMU_DEBUG
-          if (kk >= S.jc[p] || p >= (uint32_t)sn) {
-            printf("bad pool entry k=%u/%u p=%u kk=%u jc=%u epos=%u sn=%d e=%u q0=%d d=%d\n", k, np, p, kk, S.jc[p], S.epos[p], sn, e, q0, d);
-            continue;
-          }
-#endif
-          stb[mrun + S.epos[p] + S.jc[p] - 1u - kk] = ((uint64_t)S.ordt[p] << 32) | pe.x;
-        }
-        mrun += s_tot;
-        lds_barrier();
-        if (tid == 0) {
-          s_lastj = S.ordt[sn - 1];
-          s_pool[q0] = 0;
-        }
+        for (int k = 0; k < kI4; ++k) sl[q0].grp[tid * kI4 + k] = make_uint2(0xdeadbeefu, 0xdeadbeefu);
+        __syncthreads();
       }
-      SM4_PHASE(3);
-      // ---- slice e + kR into the freed slot
+#endif
+      // ---- slice e's matches, in arrival order of j, and slice e + kR into the freed slot: one barrier chain
       off[0] = off[1];
       cnt[0] = cnt[1];
 #pragma unroll
@@ -800,14 +897,20 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
         cnt[u] = cnt[u + 1];
       }
       off[kR - 1] = cnt[kR - 1] = 0;
-      if (e + kR < nsl) {
-        rank4(sl[q0], pre, slice_n(e + kR), lw, FP, a.err);
-        const uint32_t vv = sl[q0].kst[h];
-        off[kR - 1] = vv & 0xffffu;
-        cnt[kR - 1] = vv >> 16;
-        if (e + kR + 1 < nsl) load(e + kR + 1);  // lands during the next stack phase
+      {
+        const bool more = e + kR < nsl;
+        // the emission's wave totals lie on the slot's key runs, which are in off / cnt since the slot was ranked and
+        // are written again in F4
+        const Emit4 E{stb, mst, &s_pool[q0], &s_lastj, &s_tot, sl[q0].kst, slice_n(e)};
+        chain4<true, 5>(sl[q0], pre, more, more ? slice_n(e + kR) : 0, lw, FP, a.err, E, mrun, st_acc, st_last);
+        if (more) {
+          const uint32_t vv = sl[q0].kst[h];
+          off[kR - 1] = vv & 0xffffu;
+          cnt[kR - 1] = vv >> 16;
+          if (e + kR + 1 < nsl) load(e + kR + 1);  // lands during the next stack phase
+        }
       }
-      SM4_PHASE(0);
+      SM4_PHASE(10);
     }
     // tiles after the bucket's last record start at its end
     __syncthreads();
@@ -863,7 +966,7 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
   }
   SM4_PHASE(4);
   if (SM_STACK4_STAMPS && a.stamps && lane == 0)
-    for (int i = 0; i < 5; ++i) atomicAdd(&a.stamps[i], st_acc[i]);
+    for (int i = 0; i < kStamps4; ++i) atomicAdd(&a.stamps[i], st_acc[i]);
 }
 
 }  // namespace
