@@ -7,6 +7,7 @@
 // dumps outputs in the product's JSON shape, so tests can compare it with both the oracle and the GPU.
 #include <algorithm>
 #include <charconv>
+#include <cmath>
 #include <map>
 #include <memory>
 #include <sstream>
@@ -25,6 +26,7 @@ struct Stage {
   const sql::StreamDef* def;
   std::vector<std::vector<int64_t>> cols;  // stored widened; views are rebuilt per flush with native widths
   std::vector<std::vector<uint8_t>> nulls;
+  std::vector<uint8_t> any_null;  // per column: nulls[k] is kept (from the first null of the staged rows on)
   std::vector<int64_t> row_pos;
   int64_t rows = 0;
 };
@@ -106,6 +108,8 @@ void json_val(std::ostringstream& o, const HApp* a, const DVal& v, int t) {
     case T_BOOL: o << (v.i ? "true" : "false"); break;
     case T_FLOAT:
     case T_DOUBLE: {
+      if (std::isnan(v.d)) { o << "\"NaN\""; break; }
+      if (std::isinf(v.d)) { o << (v.d > 0 ? "\"Infinity\"" : "\"-Infinity\""); break; }
       char b[64];
       auto r = std::to_chars(b, b + 64, v.d);
       std::string s(b, r.ptr);
@@ -329,6 +333,7 @@ void flush(HApp* a) {
   for (auto& S : a->st) {
     for (auto& c : S.cols) c.clear();
     for (auto& c : S.nulls) c.clear();
+    std::fill(S.any_null.begin(), S.any_null.end(), 0);
     S.row_pos.clear();
     S.rows = 0;
   }
@@ -366,10 +371,13 @@ int h_create(const char* text, void** out, char* err, size_t len) {
   try {
     a->ast = sql::parse_app(text);
     for (auto& s : a->ast.streams) {
+      // NfaStream holds kMaxAttrs columns; an inferred output stream counts (runtime.cpp upload_app refuses it too)
+      if (s.attrs.size() > (size_t)kMaxAttrs) throw sql::UnsupportedError("stream has too many attributes");
       Stage S;
       S.def = &s;
       S.cols.resize(s.attrs.size());
       S.nulls.resize(s.attrs.size());
+      S.any_null.assign(s.attrs.size(), 0);
       a->st.push_back(std::move(S));
     }
     for (auto& p : a->ast.partitions) a->parts.push_back(compile_partition(a->ast, p, a->dict));
@@ -422,8 +430,11 @@ int h_send(void* h, const char* sid, int64_t ts, const hv* row) {
       else x = row[k].i;
     } else if (t == T_STRING) x = -1;
     S.cols[k].push_back(x);
-    if (isnull && S.nulls[k].empty()) S.nulls[k].assign(S.rows, 0);
-    if (!S.nulls[k].empty()) S.nulls[k].push_back(isnull);
+    if (isnull && !S.any_null[k]) {  // a flag, not nulls[k].empty(): a null in the first staged row leaves the mask empty
+      S.any_null[k] = 1;
+      S.nulls[k].assign(S.rows, 0);
+    }
+    if (S.any_null[k]) S.nulls[k].push_back(isnull);
   }
   S.row_pos.push_back((int64_t)a->ev_stream.size());
   stage(a, s, S.rows, ts, 0);

@@ -17,11 +17,13 @@ def plans():
     import bench
     import synth
     from test_device_events import VARIANTS
+    from test_device_expr import jit_plans
     apps = {"bench_config5": bench.APP5}
     for k, v in VARIANTS.items():
         apps[f"device_events_{k}"] = synth.app5(v)
     for k, v in bench.VARIANTS5.items():
         apps[f"bench_{k}"] = bench.app5_variant(v)
+    apps.update(jit_plans())
     return apps
 
 
@@ -48,13 +50,16 @@ def main():
     a = ap.parse_args()
     if a.one:
         sys.exit(one(a.one))
-    env = dict(os.environ, SM_NFA_JIT_COMPACT="1")
+    # the lane-record form a batch launch compiles for (nfa.hip lane_compact_ok): events of at most 4 attributes take
+    # the compact record; the 13-attribute events of tests/test_device_expr.py do not
+    envs = {c: dict(os.environ, SM_NFA_JIT_COMPACT=c) for c in "01"}
     names = a.only.split(",") if a.only else list(plans())
     procs, rc = [], 0
     while names or procs:
         while names and len(procs) < a.j:
             name = names.pop(0)
-            procs.append(subprocess.Popen([sys.executable, __file__, "--one", name], env=env))
+            procs.append(subprocess.Popen([sys.executable, __file__, "--one", name],
+                                          env=envs["0" if name.startswith("device_expr_") else "1"]))
         p = procs.pop(0)
         rc |= p.wait()
     sys.exit(rc)
