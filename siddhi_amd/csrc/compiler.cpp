@@ -867,6 +867,66 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
         }
       }
     }
+    // ---- its k-state sibling over several streams of one schema, 3 <= k <= 8: every e1=S1[c1] -> e2=S2[c2] within T2
+    // -> ... -> ek=Sk[ck] within Tk (kernels/mpatk_dev.h). A within on every element after the first is part of the
+    // form, as above. S1 is none of S2 .. S(k-1): the hand-over to the NFA kernel replays the bound events of the open
+    // partials, and a replayed e2 .. e(k-1) on S1's stream that passes c1 would open a partial a second time
+    if (q.input == InputKind::PATTERN && root_el->kind == StateKind::NEXT && !root_el->has_within && !q.having) {
+      std::vector<const StateElem*> leaves;
+      bool ok = true;
+      std::function<void(const StateElem*, bool)> walk = [&](const StateElem* el, bool first) {
+        if (el->kind == StateKind::NEXT) {
+          if (el->has_within) ok = false;  // a parenthesised sub-chain with its own within
+          walk(el->a.get(), first);
+          walk(el->b.get(), false);
+        } else if (el->kind == StateKind::EVERY && first && leaves.empty() && !el->has_within &&
+                   el->a->kind == StateKind::STREAM && !el->a->has_within) {
+          leaves.push_back(el->a.get());
+        } else if (el->kind == StateKind::STREAM && !leaves.empty() && el->has_within) {
+          leaves.push_back(el);
+        } else {
+          ok = false;
+        }
+      };
+      walk(root_el, true);
+      const int k = (int)leaves.size();
+      ok = ok && k >= 3 && k <= 8 && h.nslots == k && (int)pres.size() == k;
+      for (int m = 0; ok && m < k; ++m) {  // (S2 is not S1: at least two streams)
+        ok = pres[m].kind == PK_STREAM && pres[m].stateId == m;
+        if (m > 0 && m < k - 1 && leaves[m]->stream_id == leaves[0]->stream_id) ok = false;
+      }
+      for (size_t r = 0; ok && r < refs.size(); r += 2)
+        if (!(refs[r + 1] == 0 || refs[r + 1] == kCurrent)) ok = false;
+      std::vector<int> keycol(app.streams.size(), -1);
+      for (int m = 0; ok && m < k; ++m) {
+        const int si = lw.metas[m].stream;
+        const StreamDef& d0 = app.streams[lw.metas[0].stream];
+        const StreamDef& d = app.streams[si];
+        ok = d.attrs.size() == d0.attrs.size();
+        for (size_t c = 0; ok && c < d.attrs.size(); ++c) ok = d.attrs[c].type == d0.attrs[c].type;
+        if (!ok || partition < 0) continue;
+        // partitioned: every read stream keyed by one INT / LONG attribute of its own
+        ok = false;
+        for (auto& w : app.partitions[partition].with)
+          if (w.stream_id == d.id && w.key->kind == ExprKind::VAR && w.key->stream_ref.empty()) {
+            const int c = d.index_of(w.key->attr);
+            if (c >= 0 && (d.attrs[c].type == AttrType::INT || d.attrs[c].type == AttrType::LONG)) {
+              keycol[si] = c;
+              ok = true;
+            }
+          }
+      }
+      if (ok) {
+        cq.fast_pat_k = k;
+        cq.fast_patk_keycol = keycol;
+        for (int m = 0; m < k; ++m) {
+          cq.fast_patk_stream[m] = lw.metas[m].stream;
+          cq.fast_patk_off[m] = pres[m].progOff;
+          cq.fast_patk_len[m] = pres[m].progLen;
+          cq.fast_patk_within[m] = m > 0 ? leaves[m]->within_ms : -1;
+        }
+      }
+    }
   }
   h.npre = (int)pres.size();
   h.npost = (int)posts.size();
@@ -880,6 +940,7 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
   }
   for (int m = 0; m < cq.fast_seq_k; ++m) refs.insert(refs.end(), {m, 0});  // hidden (e1, ..., ek) ordinals, likewise
   for (int m = 0; m < cq.fast_seq_ms; ++m) refs.insert(refs.end(), {m, 0});
+  for (int m = 0; m < cq.fast_pat_k; ++m) refs.insert(refs.end(), {m, 0});
   h.nrefs = (int)refs.size() / 2;
   h.nconst = (int)consts.size();
   // per-key state layout (int64 words)

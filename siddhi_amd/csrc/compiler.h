@@ -72,8 +72,22 @@ struct CompiledQuery {
   int fast_pat_off[2] = {0, 0}, fast_pat_len[2] = {0, 0};
   int64_t fast_pat_within = -1;
   std::vector<int> fast_pat_keycol;
+  // fast path: every e1=S1[c1] -> e2=S2[c2] within T2 -> ... -> ek=Sk[ck] within Tk with 3 <= k <= 8 over at least two
+  // streams of one schema, S1 none of S2 .. S(k-1) (pattern: every S1 event passing c1 binds, state by state, the first
+  // later Sm event of its partition instance that passes cm, each inside Tm of the event bound before it;
+  // kernels/mpatk_dev.h). fast_pat_k = k (0: not this form), a mark of its own: such a query runs through the
+  // interleaved entry point only. Per element m its app stream, its condition program (state context, slots 0..m) and
+  // its within against the previous element's event (>= 0 for m >= 1; element 0 has none). fast_patk_keycol[s] as
+  // fast_ms_keycol. The plan carries k hidden ordinal refs (slot m, index 0) after the visible ones.
+  int fast_pat_k = 0;
+  int fast_patk_stream[8] = {0};
+  int fast_patk_off[8] = {0}, fast_patk_len[8] = {0};
+  int64_t fast_patk_within[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+  std::vector<int> fast_patk_keycol;
   // uint32 words per device match tuple: k, 2 for every other state query, 1 for a filter (its kept row)
-  int match_arity() const { return hdr.kind == 0 ? 1 : fast_seq_k ? fast_seq_k : fast_seq_ms ? fast_seq_ms : 2; }
+  int match_arity() const {
+    return hdr.kind == 0 ? 1 : fast_seq_k ? fast_seq_k : fast_seq_ms ? fast_seq_ms : fast_pat_k ? fast_pat_k : 2;
+  }
 };
 
 struct CompiledPartition {

@@ -43,7 +43,8 @@ struct FastState {
   int sort_wgs_per_cu = 0;  // resident down-sweep workgroups per CU (persistent-chunk grid)
   int walk_wgs_per_cu = 0;  // resident walk workgroups per CU
   // pipeline of the last batch: 2 = sort / walk, 3 = bucket stack; seqpath.hip: 6 = adjacent pairs, 7 = adjacent runs,
-  // 8 = adjacent runs over several streams, 9 = the pattern over two streams
+  // 8 = adjacent runs over several streams, 9 = the pattern over two streams, 10 = the k-state pattern over several
+  // streams
   int last_path = 0;
 };
 
@@ -75,10 +76,17 @@ struct FastCarry {
   int width = 0;            // 3 + nattr
   bool active = false;      // a device batch has run for this query: ts_last is valid
   int64_t ts_last = 0;      // event time of the last event of the last batch
+  // fast_pat_k only: the open partials [key, bound events s, global ordinals o1 .. os padded to k - 1], every key's in
+  // order of o1; `rows` are then the events they hold, each once, with the stream as the last word
+  int64_t* parts = nullptr;  // device, pn rows of pw words
+  int64_t pn = 0, pcap = 0;
+  int pw = 0;               // k + 1
   void reserve(int64_t rows_needed, int w);
+  void reserve_parts(int64_t rows_needed, int w, hipStream_t s);  // the old rows are not kept
   void release();
   void reset() {
     n = 0;
+    pn = 0;
     active = false;
     ts_last = 0;
   }
@@ -164,6 +172,23 @@ struct MPatPlan : MSeqKeys {
 // carry or pairs_out is touched. Sets fs.last_path = 9.
 int64_t fast_pat_ms(const FastArgs& a, const int32_t* sid, const MPatPlan& p, int nattr, FastState& fs, FastCarry& carry,
                     uint32_t* pairs_out, int64_t pairs_cap, Scratch& sc, hipStream_t s, FastTimings* tm = nullptr);
+
+// Its k-state sibling `every e1=S1[c1] -> e2=S2[c2] within T2 -> ... -> ek=Sk[ck] within Tk`, 3 <= k <= 8 (seqpath.hip,
+// mpatk_dev.h has the rule and the kernels). within[m] >= 0 for every m >= 1, against the event bound before.
+struct MPatKPlan : MSeqKeys {
+  int k = 0;
+  int stream[8] = {0};
+  int off[8] = {0}, len[8] = {0};
+  int64_t within[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+};
+
+// a.st, `sid`, key_remap and FAST_KEY_SPAN as fast_seq_ms. Outputs are k-tuples as fast_seq_k's (members carried from
+// earlier batches negative as int32), in lexicographic order of (ek, ..., e1), at most n + carry.pn of them (tuples_cap).
+// The carry holds the open partials (FastCarry::parts) and the events they have bound, each once, as fast_seq_ms's rows
+// of 4 + nattr words. FAST_NON_MONOTONE: the event time of the read rows decreases inside the batch or against
+// carry.ts_last. Every error result is returned before the carry or tuples_out is touched. Sets fs.last_path = 10.
+int64_t fast_pat_k(const FastArgs& a, const int32_t* sid, const MPatKPlan& p, int nattr, FastState& fs, FastCarry& carry,
+                   uint32_t* tuples_out, int64_t tuples_cap, Scratch& sc, hipStream_t s, FastTimings* tm = nullptr);
 
 // keys[i] = the partition key of row i (the key column of its own stream, as int64), 0 for a row that is not read: the
 // one key column remap_keys takes when an interleaved batch's keys become dense ids

@@ -1,5 +1,5 @@
-// Host entries of the four sequence closed forms (fastpath.h has their contracts, seq_dev.h / mseq_dev.h / mpat_dev.h
-// the rules and the kernels). Every driver runs one batch through the same stages, each written once below:
+// Host entries of the five sequence closed forms (fastpath.h has their contracts, seq_dev.h / mseq_dev.h / mpat_dev.h /
+// mpatk_dev.h the rules and the kernels). Every driver runs one batch through the same stages, each written once below:
 //   begin      Batch: the timing start, the scratch mark, and leave(), which every return goes through
 //   facts      one streaming pass over the keys, event times and ordinals, plus the carried ordinals; its read-back is
 //              the only host round trip before anything is changed (Facts: the same fields for SeqFacts and MSeqFacts)
@@ -26,10 +26,15 @@
 //   fast_pat_ms        path 9: packed as path 8; mpat_link_kernel writes each partial's e2 at the e1's own place; the pairs
 //                      are compacted in order of e1 after the counts are known, then sorted by e2 alone (the reference's
 //                      (e2, e1) order); the carry build's room is checked again once the candidates are counted
+//   fast_pat_k         path 10: packed as path 8; mpatk_link_kernel walks each partial through its states and writes ek at
+//                      the e1's own place; the k-tuples are compacted in order of e1, then sorted by e2, ..., ek in turn;
+//                      the carry is two tables, the open partials and (path 8's rows, through build_carry) the events
+//                      they hold, each once: the link pass flags them, mpatk_cand_kernel makes the candidates
 #include <string>
 
 #include "fastpath.h"
 #include "mpat_dev.h"
+#include "mpatk_dev.h"
 #include "mseq_dev.h"
 #include "seq_dev.h"
 
@@ -139,6 +144,9 @@ constexpr Labels kMSeqLabels = {"mseq_facts", "mseq_pack", "mseq_sort",  "mseq_k
 constexpr Labels kMPatLabels = {"mpat_facts", "mpat_pack", "mpat_sort",  nullptr,
                                 "mpat_count", "mpat_scan", "mpat_emit",  "mpat_carry",
                                 "pattern closed form over two streams"};
+constexpr Labels kMPatKLabels = {"mpatk_facts", "mpatk_pack", "mpatk_sort",  "mpatk_cand",
+                                 "mpatk_count", "mpatk_scan", "mpatk_emit",  "mpatk_carry",
+                                 "k-state pattern closed form over several streams"};
 
 // ---- begin / leave. own_marks: the driver's marks are the batch's only ones (same-stream); otherwise the entry
 // point's own marks come first, and the first label here times from the last of them
@@ -797,6 +805,183 @@ int64_t fast_pat_ms(const FastArgs& a, const int32_t* sid, const MPatPlan& p, in
     b.mark("mpat_order");
   }
   return carry_out(b, a, o, ncand, nattr, h.ts_last, carry, fs, 9, L, m);
+}
+
+int64_t fast_pat_k(const FastArgs& a, const int32_t* sid, const MPatKPlan& p, int nattr, FastState& fs, FastCarry& carry,
+                   uint32_t* tuples_out, int64_t tuples_cap, Scratch& sc, hipStream_t s, FastTimings* tm) {
+  const Labels& L = kMPatKLabels;
+  const int64_t n = a.n;
+  const int k = p.k, pw = k + 1;
+  if (k < 3 || k > kSeqKMax) return FAST_OUTSIDE;
+  if (n == 0) return 0;
+  const int64_t ne = carry.n, ncp = carry.pn;
+  if (n >= 0x7fffffffll || n + ncp >= 0x7fffffffll || n + ne >= 0x7fffffffll) return FAST_OUTSIDE;
+  for (int m = 0; m < k; ++m)
+    if (p.stream[m] < 0 || p.stream[m] >= kMSeqStreams || (m > 0 && p.within[m] < 0)) return FAST_OUTSIDE;
+  if (ncp > 0 && carry.pw != pw) return FAST_OUTSIDE;
+  const bool keyed = p.keyed;
+  Batch b(sc, s, tm, false);
+  const int cw = 4 + nattr;
+  const int64_t ntiles = (n + kSeqTile - 1) / kSeqTile;
+
+  MSeqSrc src = mseq_src(n, sid, p);
+  src.ts = a.ts;
+  src.ordinals = a.ordinals;
+  src.obase = a.ordinal_base;
+
+  uint32_t* tile_n;
+  const Facts h = mseq_facts(b, a, src, keyed, ntiles, carry, L.facts, &tile_n);
+  const int64_t np = h.np;
+  int kbits;
+  if (const int64_t r = envelope(h, true, keyed, np + ncp <= tuples_cap, carry, cw, p.remap_span, &kbits))
+    return b.leave(r);
+  if (np == 0) {  // no row of a stream the query reads: its carried partials wait
+    fs.last_path = 10;
+    return b.leave(0);
+  }
+  const bool wide = kbits > 32;
+
+  const int64_t cand_cap = np + ne;  // every read row and every carried event at most once
+  const int64_t total = ncp + n;     // entries of res / kept, rows of mid
+  const int64_t rtiles = (total + kSeqTile - 1) / kSeqTile;
+  const size_t hist = (size_t)8 << 20;
+  {  // scratch up to the counts, for the worst case, before anything changes. Per read row: sort pairs twice over (+ a
+     // histogram word per 4 rows) and a stream byte; per entry: result, kept and k - 1 members; a flag per event
+    const size_t link = (size_t)np * (keyed ? (wide ? 27 : 19) : 6) + (size_t)total * 4 * (size_t)(k + 1) + (size_t)(ne + n) +
+                        (size_t)(ntiles + 2 * rtiles + 8) * 8 + hist;
+    if (sc.used + (size_t)cand_cap * 32 + link + 8192 > sc.cap) return b.leave(FAST_OUTSIDE);
+  }
+  uint32_t* npart = (uint32_t*)sc.take(8);  // the partials that stay
+  const Out o = take_out(sc, cand_cap);
+
+  const Rows rows = mseq_pack_sort(b, src, tile_n, ntiles, np, keyed, h.kmin, kbits, L);
+  b.event(1);
+
+  // ---- link: every partial (carried ones, then S1 rows passing c1) walks its key run through its states
+  SM_HIP(hipMemsetAsync(o.ctl, 0, 8, s));
+  MPatKArgs ma{};
+  ma.np = np;
+  ma.n = n;
+  ma.ts = a.ts;
+  ma.st = a.st;
+  ma.code = a.code;
+  ma.consts = a.consts;
+  ma.k = k;
+  for (int m = 0; m < kSeqKMax; ++m) {
+    ma.off[m] = m < k ? p.off[m] : 0;
+    ma.len[m] = m < k ? p.len[m] : 0;
+    ma.within[m] = m > 0 && m < k ? p.within[m] : 0;
+    ma.want[m] = m < k ? p.stream[m] : -2;
+  }
+  ma.ts_last = h.ts_last;
+  ma.ordinals = a.ordinals;
+  ma.obase = a.ordinal_base;
+  ma.perm = rows.perm;
+  ma.skey = rows.skey;
+  ma.kmin = h.kmin;
+  ma.kmax = h.kmax;
+  ma.sstr = rows.sstr;
+  ma.sid = sid;
+  ma.evt = (const int64_t*)carry.rows;
+  ma.ne = ne;
+  ma.cw = cw;
+  ma.parts = (const int64_t*)carry.parts;
+  ma.ncp = ncp;
+  ma.res = (int32_t*)sc.take((size_t)total * 4);
+  ma.kept = (int32_t*)sc.take((size_t)total * 4);
+  ma.mid = (int32_t*)sc.take((size_t)total * 4 * (size_t)(k - 1));
+  ma.eflag = (uint8_t*)sc.take((size_t)(ne + n));
+  uint32_t* counts = (uint32_t*)sc.take((size_t)(rtiles + 1) * 4);
+  uint32_t* kcounts = (uint32_t*)sc.take((size_t)(rtiles + 1) * 4);
+  SM_HIP(hipMemsetAsync(ma.eflag, 0, (size_t)(ne + n), s));
+  // rows that are not read have no lane: their entries are "none"
+  if (np < n) {
+    SM_HIP(hipMemsetD32Async((hipDeviceptr_t)(ma.res + ncp), (int)kSeqNone, (size_t)n, s));
+    SM_HIP(hipMemsetD32Async((hipDeviceptr_t)(ma.kept + ncp), (int)kSeqNone, (size_t)n, s));
+  }
+  const dim3 lgrid((unsigned)((ncp + np + kSeqTile - 1) / kSeqTile)), block(kSeqBlock);
+  if (wide) hipLaunchKernelGGL(mpatk_link_kernel<uint64_t>, lgrid, block, 0, s, ma);
+  else hipLaunchKernelGGL(mpatk_link_kernel<uint32_t>, lgrid, block, 0, s, ma);
+  b.mark("mpatk_link");
+  b.event(2);
+
+  // ---- the three counts: tuples, partials that stay, and the events they hold
+  const dim3 rgrid((unsigned)rtiles);
+  hipLaunchKernelGGL(seq_count_kernel, rgrid, block, 0, s, (const int32_t*)ma.res, total, counts);
+  hipLaunchKernelGGL(seq_count_kernel, rgrid, block, 0, s, (const int32_t*)ma.kept, total, kcounts);
+  b.mark(L.count);
+  exclusive_scan_u32(counts, (size_t)rtiles, sc, s, o.ctl + 1);
+  exclusive_scan_u32(kcounts, (size_t)rtiles, sc, s, npart);
+  b.mark(L.scan);
+  MPatKCand ca{};
+  ca.s = src;
+  ca.evt = ma.evt;
+  ca.ne = ne;
+  ca.cw = cw;
+  ca.eflag = ma.eflag;
+  ca.cand = o.cand;
+  ca.cand_n = o.ctl;
+  hipLaunchKernelGGL(mpatk_cand_kernel, seq_grid(ne + n, kSeqBlock), block, 0, s, ca);
+  b.mark(L.keep);
+  uint32_t hpart = 0;
+  SM_HIP(hipMemcpyAsync(&hpart, npart, 4, hipMemcpyDeviceToHost, s));
+  int64_t ncand;
+  const int64_t m = read_counts(b, o, tuples_cap, L, &ncand);
+  const int64_t pk = hpart;
+  // room for the tuples' sorts, the new partials and the carry build, now that the counts are known: still nothing is
+  // changed
+  // (per tuple: k words, two sort pairs and, as per read row above, a histogram word per 4 tuples for the sorts)
+  if (sc.used + (size_t)m * (size_t)(4 * k + 17) + (size_t)pk * pw * 8 + hist + 8192 > sc.cap ||
+      o.keep + (size_t)ncand * (size_t)(8 * cw + 44) + hist + 4096 > sc.cap)
+    return b.leave(FAST_OUTSIDE);
+
+  MPatKOut oa{};
+  oa.s = src;
+  oa.total = total;
+  oa.ncp = ncp;
+  oa.mid = ma.mid;
+  oa.k = k;
+  oa.evt = ma.evt;
+  oa.cw = cw;
+  oa.parts = ma.parts;
+  // ---- the tuples in order of e1 (carried partials in their order, then row order), then stable sorts by e2, e3, ...,
+  // ek in turn: the reference's (ek, ..., e1) order. ek is a batch row; an earlier member may be carried (negative)
+  if (m > 0) {
+    uint32_t* tup = (uint32_t*)sc.take((size_t)m * 4 * (size_t)k);
+    uint32_t* key = (uint32_t*)sc.take((size_t)m * 4);
+    uint32_t* key2 = (uint32_t*)sc.take((size_t)m * 4);
+    uint32_t* idx = (uint32_t*)sc.take((size_t)m * 4);
+    uint32_t* idx2 = (uint32_t*)sc.take((size_t)m * 4);
+    oa.flags = ma.res;
+    oa.offsets = counts;
+    oa.tuples = tup;
+    hipLaunchKernelGGL(mpatk_emit_kernel, rgrid, block, 0, s, oa);
+    b.mark(L.emit);
+    const int obits = std::max(1, bits_of((uint64_t)h.omax));
+    for (int slot = 1; slot < k; ++slot) {  // idx: the tuples' order so far (the first pass writes 0 .. m - 1)
+      const bool flip = slot < k - 1 && ne > 0;
+      hipLaunchKernelGGL(mpatk_keys_kernel, seq_grid(m, kSeqBlock), block, 0, s, (const uint32_t*)tup, k, slot,
+                         slot == 1 ? (const uint32_t*)nullptr : (const uint32_t*)idx, m, flip ? 0x80000000u : 0u, key, idx);
+      if (sort_pairs(false, key, key2, idx, idx2, m, flip ? 32 : obits, b)) std::swap(idx, idx2);
+    }
+    hipLaunchKernelGGL(mpatk_tuples_kernel, seq_grid(m, kSeqBlock), block, 0, s, (const uint32_t*)tup, k,
+                       (const uint32_t*)idx, m, tuples_out);
+    b.mark("mpatk_order");
+  }
+  // ---- the partials that stay (the old ones are read until here), then their events
+  if (pk > 0) {
+    int64_t* pout = (int64_t*)sc.take((size_t)pk * pw * 8);
+    oa.flags = ma.kept;
+    oa.offsets = kcounts;
+    oa.parts_out = pout;
+    hipLaunchKernelGGL(mpatk_parts_kernel, rgrid, block, 0, s, oa);
+    carry.reserve_parts(pk, pw, s);
+    SM_HIP(hipMemcpyAsync(carry.parts, pout, (size_t)pk * pw * 8, hipMemcpyDeviceToDevice, s));
+    b.mark("mpatk_parts");
+  }
+  carry.pn = pk;
+  carry.pw = pw;
+  return carry_out(b, a, o, ncand, nattr, h.ts_last, carry, fs, 10, L, m, false, sid);
 }
 
 }  // namespace sm

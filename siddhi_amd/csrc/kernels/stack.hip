@@ -778,10 +778,23 @@ void FastCarry::reserve(int64_t rows_needed, int w) {
   width = w;
 }
 
+void FastCarry::reserve_parts(int64_t rows_needed, int w, hipStream_t s) {
+  if (rows_needed * w <= pcap) return;
+  SM_HIP(hipStreamSynchronize(s));  // kernels in flight may read the old rows
+  int64_t* p = nullptr;
+  const int64_t c = std::max<int64_t>(rows_needed * w, std::max<int64_t>(pcap * 2, 4096));
+  SM_HIP(hipMalloc(&p, (size_t)c * 8));
+  if (parts) SM_HIP(hipFree(parts));
+  parts = p;
+  pcap = c;
+}
+
 void FastCarry::release() {
   if (rows) (void)hipFree(rows);
-  rows = nullptr;
+  if (parts) (void)hipFree(parts);
+  rows = parts = nullptr;
   cap = n = 0;
+  pcap = pn = 0;
 }
 
 void build_carry(const int64_t* cand, int64_t ncand, const NfaStream* st, int nattr, FastCarry& carry, Scratch& sc,

@@ -1245,7 +1245,7 @@ void read_outputs(sm_app* a, int qidx, const void* dev, int64_t n, std::vector<H
     const int64_t* rf = (const int64_t*)(b + sizeof(OutRec) + cq.hdr.nsel * sizeof(DVal));
     h.refs = rf;
     h.nrefs = cq.hdr.nrefs_vis;
-    if (cq.fast_seq_k || cq.fast_seq_ms) {  // k hidden refs: the match's events in slot order
+    if (cq.fast_seq_k || cq.fast_seq_ms || cq.fast_pat_k) {  // k hidden refs: the match's events in slot order
       h.tuple = rf + cq.hdr.nrefs_vis;
       h.e1 = h.tuple[0];
       h.e2 = h.tuple[cq.match_arity() - 1];
@@ -1691,8 +1691,11 @@ int64_t nfa_device_batch(sm_app* a, int qi, int s, size_t n, const int64_t* d_ts
 // for good: each instance's carried rows (its last k - 1 read events at most, each with its stream in the row's last
 // word) are replayed on their own streams, every key's in ordinal order, as a batch of their own in front of whatever
 // comes next. Fewer than k events per instance emit nothing and leave the NFA in the state the rule implies (a
-// partial's life is one event, so the state is a function of the last k - 1 events). The playback clock is left alone,
-// as in nfa_device_batch. The caller's event-index arrays (d_ev_*, d_adv_*) are overwritten.
+// partial's life is one event, so the state is a function of the last k - 1 events). The k-state pattern over several
+// streams (fast_pat_k, path 10) carries rows of the same form, the events its open partials have bound, each once:
+// replayed in (key, ordinal) order they bind again what they bound (S1 is none of S2 .. S(k-1), so none of them opens a
+// partial twice) and emit nothing, since no ek is among them; its partial table is dropped with the rows. The playback
+// clock is left alone, as in nfa_device_batch. The caller's event-index arrays (d_ev_*, d_adv_*) are overwritten.
 void mseq_replay_carry(sm_app* a, int qi, hipStream_t hs) {
   QueryRt& q = *a->queries[qi];
   const int64_t nc = q.nfa_mode ? 0 : q.carry.n;
@@ -2778,7 +2781,9 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
   }
 }
 
-// The closed forms over one interleaved device batch (sm_app_process_device_events; seqpath.hip): a sequence over
+// The closed forms over one interleaved device batch (sm_app_process_device_events; seqpath.hip): the k-state pattern
+// over several streams (CompiledQuery::fast_pat_k, fast_pat_k, path 10: k-tuples in dev_pairs, carried members projected
+// from prev_carry, the carried events), a sequence over
 // several streams of one schema (CompiledQuery::fast_seq_ms, fast_seq_ms, path 8: k-tuples in dev_pairs) or the pattern
 // `every e1=A -> e2=B within T` over two streams (CompiledQuery::fast_pat_ms, fast_pat_ms, path 9: (e1, e2) pairs, an e1
 // carried from an earlier batch projected from prev_carry). `nst` are the host copies of the batch's stream
@@ -2806,8 +2811,19 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
   fa.ordinal_base = ordinal_base;
   MSeqPlan sp;
   MPatPlan pp;
+  MPatKPlan kp;
+  const int patk = cq.fast_pat_k;
   std::vector<int> read;  // the streams the query reads
-  if (pat) {
+  if (patk) {
+    kp.k = patk;
+    for (int m = 0; m < patk; ++m) {
+      kp.stream[m] = cq.fast_patk_stream[m];
+      kp.off[m] = cq.fast_patk_off[m];
+      kp.len[m] = cq.fast_patk_len[m];
+      kp.within[m] = cq.fast_patk_within[m];
+    }
+    read = cq.streams;
+  } else if (pat) {
     for (int m = 0; m < 2; ++m) {
       pp.stream[m] = cq.fast_pat_stream[m];
       pp.off[m] = cq.fast_pat_off[m];
@@ -2825,12 +2841,12 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
     }
     read = cq.streams;
   }
-  MSeqKeys& keys = pat ? static_cast<MSeqKeys&>(pp) : sp;
+  MSeqKeys& keys = patk ? static_cast<MSeqKeys&>(kp) : pat ? static_cast<MSeqKeys&>(pp) : sp;
   keys.keyed = cq.partition >= 0;
   for (int s : read) {  // every read stream's own key attribute
     keys.read |= 1ull << s;
     if (!keys.keyed) continue;
-    const int c = (pat ? cq.fast_pat_keycol : cq.fast_ms_keycol).at(s);
+    const int c = (patk ? cq.fast_patk_keycol : pat ? cq.fast_pat_keycol : cq.fast_ms_keycol).at(s);
     keys.kcol[s] = d_cols[c];
     if (d.types[c] == T_LONG) keys.wide |= 1ull << s;
   }
@@ -2843,10 +2859,13 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
     keys.wide = 0;
   };
   // a sequence: k words per match, at most one match per event; the pattern: (e1, e2) per match, at most one per partial
-  const int64_t cap = pat ? (int64_t)n + q.carry.n : (int64_t)n;
-  q.dev_pairs.ensure(std::max<size_t>(pat ? (size_t)cap * 8 : n * 4 * (size_t)sp.k, 16));
+  // the k-state pattern: k words per match, at most one per partial
+  const int64_t cap = patk ? (int64_t)n + q.carry.pn : pat ? (int64_t)n + q.carry.n : (int64_t)n;
+  q.dev_pairs.ensure(std::max<size_t>(patk ? (size_t)cap * 4 * (size_t)patk : pat ? (size_t)cap * 8 : n * 4 * (size_t)sp.k, 16));
   FastTimings* tm = a->fast_timing ? &a->fast_tm : nullptr;
   auto closed = [&] {
+    if (patk)
+      return fast_pat_k(fa, d_stream_idx, kp, d.nattr, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, cap, a->sc, hs, tm);
     return pat ? fast_pat_ms(fa, d_stream_idx, pp, d.nattr, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, cap, a->sc, hs, tm)
                : fast_seq_ms(fa, d_stream_idx, sp, d.nattr, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, cap, a->sc, hs, tm);
   };
@@ -3120,7 +3139,7 @@ void flush(sm_app* a) {
     // (paths 8 and 9)
     for (size_t qi = 0; qi < a->queries.size(); ++qi) {
       QueryRt& q = *a->queries[qi];
-      if (!(q.cq.fast_seq_ms || q.cq.fast_pat_ms) || q.nfa_mode || q.nfa_used || !q.carry.active) continue;
+      if (!(q.cq.fast_seq_ms || q.cq.fast_pat_ms || q.cq.fast_pat_k) || q.nfa_mode || q.nfa_used || !q.carry.active) continue;
       bool staged = false;
       for (int s : q.cq.streams) staged |= a->streams[s].rows > 0;
       if (staged) mseq_replay_carry(a, (int)qi, a->stream);
@@ -3691,7 +3710,9 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
     // and every query under keep_outputs stay on the NFA kernel here, as before.
     QueryRt* msq = nullptr;
     // Likewise the pattern `every e1=A -> e2=B within T` over two streams (CompiledQuery::fast_pat_ms, path 9).
-    if (a->queries.size() == 1 && (a->queries[0]->cq.fast_seq_ms > 0 || a->queries[0]->cq.fast_pat_ms) &&
+    // And its k-state sibling (CompiledQuery::fast_pat_k, path 10).
+    if (a->queries.size() == 1 &&
+        (a->queries[0]->cq.fast_seq_ms > 0 || a->queries[0]->cq.fast_pat_ms || a->queries[0]->cq.fast_pat_k > 0) &&
         a->streams.size() <= 64)
       msq = a->queries[0].get();
     size_t need = batch_scratch(a, N);
@@ -3702,6 +3723,12 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
       // the pattern: a result word and two sort pairs per carried row too; its carry build is sized by the candidates
       // the batch leaves (fast_pat_ms checks that before anything changes)
       if (msq->cq.fast_pat_ms) need += nc * 24;
+      // the k-state pattern: result, kept and k - 1 members per row and carried partial, a flag per event, k words and
+      // two sort pairs per tuple, the new partials (fast_pat_k checks the last two once they are counted)
+      if (const size_t k = (size_t)msq->cq.fast_pat_k) {
+        const size_t pn = (size_t)msq->carry.pn;
+        need += (n + pn) * (4 * (k + 1) + 4 * k + 16 + 8 * (k + 1)) + n + nc;
+      }
     }
     ensure_scratch(a, need);
     a->sc.used = 0;
@@ -3724,7 +3751,8 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
         const CompiledQuery& cq = q.cq;
         if (ms_tuples && !q.nfa_mode && !q.nfa_used &&
             (pat ? run_progs_ok(cq, cq.fast_pat_off, cq.fast_pat_len, 2)
-                 : run_progs_ok(cq, cq.fast_ms_off, cq.fast_ms_len, cq.fast_seq_ms))) {
+                 : cq.fast_pat_k ? run_progs_ok(cq, cq.fast_patk_off, cq.fast_patk_len, cq.fast_pat_k)
+                                 : run_progs_ok(cq, cq.fast_ms_off, cq.fast_ms_len, cq.fast_seq_ms))) {
           std::vector<HostOut> douts;
           std::vector<DevOut> draw;
           a->out_arena.clear();
@@ -3880,6 +3908,15 @@ int sm_app_snapshot(sm_app* a, uint8_t* buf, size_t cap, size_t* len) {
         SM_HIP(hipMemcpy(rows.data(), q.carry.rows, rows.size() * 8, hipMemcpyDeviceToHost));
         w.raw(rows.data(), rows.size() * 8);
       }
+      if (q.cq.fast_pat_k) {  // the open partials of the k-state pattern (the rows above: the events they hold)
+        w.put<int64_t>(q.carry.pn);
+        w.put<int32_t>(q.carry.pw);
+        if (q.carry.pn > 0) {
+          std::vector<int64_t> rows((size_t)q.carry.pn * q.carry.pw);
+          SM_HIP(hipMemcpy(rows.data(), q.carry.parts, rows.size() * 8, hipMemcpyDeviceToHost));
+          w.raw(rows.data(), rows.size() * 8);
+        }
+      }
     }
     *len = w.b.size();
     if (buf && cap >= w.b.size()) memcpy(buf, w.b.data(), w.b.size());
@@ -3992,14 +4029,46 @@ int sm_app_restore(sm_app* a, const uint8_t* buf, size_t len) {
       const int64_t cn = r.get<int64_t>();
       const int32_t cw = r.get<int32_t>();
       if (cn < 0 || cw < 0 || (cn > 0 && cw < 3)) throw std::runtime_error("CannotRestoreSiddhiAppStateException: bad carry");
+      std::vector<int64_t> crows((size_t)cn * cw);
       if (cn > 0) {
-        std::vector<int64_t> rows((size_t)cn * cw);
-        r.raw(rows.data(), rows.size() * 8);
+        r.raw(crows.data(), crows.size() * 8);
         q.carry.reserve(cn, cw);
-        SM_HIP(hipMemcpy(q.carry.rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice));
+        SM_HIP(hipMemcpy(q.carry.rows, crows.data(), crows.size() * 8, hipMemcpyHostToDevice));
         q.carry.n = cn;
       }
       q.carry.width = cw;
+      if (q.cq.fast_pat_k) {
+        const int64_t pn = r.get<int64_t>();
+        const int32_t pw = r.get<int32_t>();
+        if (pn < 0 || (pn > 0 && pw != q.cq.fast_pat_k + 1))
+          throw std::runtime_error("CannotRestoreSiddhiAppStateException: bad carry");
+        if (pn > 0) {
+          std::vector<int64_t> rows((size_t)pn * pw);
+          r.raw(rows.data(), rows.size() * 8);
+          // every partial holds 1 .. k - 1 events, each a row of the event table (sorted by (key, ordinal)): the link
+          // kernel would drop a partial whose event it does not find
+          auto held = [&](int64_t key, int64_t ord) {
+            int64_t lo = 0, hi = cn;
+            while (lo < hi) {
+              const int64_t mid = (lo + hi) >> 1;
+              const int64_t* e = crows.data() + mid * cw;
+              if (e[0] < key || (e[0] == key && e[1] < ord)) lo = mid + 1;
+              else hi = mid;
+            }
+            return lo < cn && crows[lo * cw] == key && crows[lo * cw + 1] == ord;
+          };
+          for (int64_t c = 0; c < pn; ++c) {
+            const int64_t* pr = rows.data() + c * pw;
+            bool ok = pr[1] >= 1 && pr[1] < q.cq.fast_pat_k;
+            for (int64_t i = 0; ok && i < pr[1]; ++i) ok = held(pr[0], pr[2 + i]);
+            if (!ok) throw std::runtime_error("CannotRestoreSiddhiAppStateException: bad carry");
+          }
+          q.carry.reserve_parts(pn, pw, a->stream);
+          SM_HIP(hipMemcpy(q.carry.parts, rows.data(), rows.size() * 8, hipMemcpyHostToDevice));
+        }
+        q.carry.pn = pn;
+        q.carry.pw = pw;
+      }
     }
     if (r.o != len) throw std::runtime_error("CannotRestoreSiddhiAppStateException: trailing bytes");
   });

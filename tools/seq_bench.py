@@ -19,6 +19,9 @@ fast_timing. Each step starts from a fresh runtime state (option reset), as benc
     python tools/seq_bench.py --query pattern_streams ...   # the pattern `every e1=A[c1] -> e2=B[c2] within T` on the same
                                                         # two-way stream index: fast_path 9 (kernels/mpat_dev.h); routes as
                                                         # for --query streams
+    python tools/seq_bench.py --query pattern_chain ...     # the three-state pattern `every e1=A[c1] -> e2=B[c2] within T
+                                                        # -> e3=A[c3] within T` on the same two-way stream index:
+                                                        # fast_path 10 (kernels/mpatk_dev.h); routes as for --query streams
 
 Step time is a host clock around work that ends in a device synchronise; a run without a GPU fails."""
 import argparse
@@ -46,14 +49,18 @@ QUERY_PAT_AB = ("@info(name='q') from every e1=A[price>20] -> e2=B[price>e1.pric
                 "select e1.timestamp as i, e2.timestamp as j insert into OutputStream;")
 QUERY_ABA = ("@info(name='q') from every e1=A[price>20], e2=B[price>e1.price], e3=A[price>e2.price] within 1 sec "
              "select e1.timestamp as i, e2.timestamp as j, e3.timestamp as l insert into OutputStream;")
+QUERY_PAT_ABA = ("@info(name='q') from every e1=A[price>20] -> e2=B[price>e1.price] within 1 sec -> "
+                 "e3=A[price>e2.price] within 1 sec "
+                 "select e1.timestamp as i, e2.timestamp as j, e3.timestamp as l insert into OutputStream;")
 
 
-STREAM_QUERIES = ("streams", "streams3", "pattern_streams")
+STREAM_QUERIES = ("streams", "streams3", "pattern_streams", "pattern_chain")
 
 
 def apps(query):
     if query in STREAM_QUERIES:
-        q = {"streams": QUERY_AB, "streams3": QUERY_ABA, "pattern_streams": QUERY_PAT_AB}[query]
+        q = {"streams": QUERY_AB, "streams3": QUERY_ABA, "pattern_streams": QUERY_PAT_AB,
+             "pattern_chain": QUERY_PAT_ABA}[query]
         return {"keyed": SCHEMA_AB + "partition with (symbol of A, symbol of B) begin " + q + " end;",
                 "unkeyed": SCHEMA_AB + q}
     q = QUERY3 if query == "three" else QUERY
@@ -67,6 +74,8 @@ LABELS += ["event_index", "mseq_facts", "mseq_pack", "mseq_sort", "mseq_link", "
            "mseq_emit", "mseq_carry"]
 LABELS += ["mpat_facts", "mpat_pack", "mpat_sort", "mpat_link", "mpat_count", "mpat_scan", "mpat_emit", "mpat_order",
            "mpat_carry"]
+LABELS += ["mpatk_facts", "mpatk_pack", "mpatk_sort", "mpatk_link", "mpatk_count", "mpatk_scan", "mpatk_cand", "mpatk_emit",
+           "mpatk_order", "mpatk_parts", "mpatk_carry"]
 
 
 def precompile(query):
@@ -103,7 +112,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--route", choices=["closed", "nfa"], default="closed")
     ap.add_argument("--forms", default="keyed,unkeyed")
-    ap.add_argument("--query", choices=["pair", "three", "streams", "streams3", "pattern_streams"], default="pair")
+    ap.add_argument("--query", choices=["pair", "three", "streams", "streams3", "pattern_streams", "pattern_chain"], default="pair")
     ap.add_argument("--precompile", action="store_true")
     ap.add_argument("--precompile-one")
     a = ap.parse_args()
