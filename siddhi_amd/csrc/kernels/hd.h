@@ -100,6 +100,8 @@ inline T __shfl_up(T v, unsigned d, int = 64) {
   const T r = sm_emu_exchange(v, l >= (int)d ? l - (int)d : l);
   return l >= (int)d ? r : v;
 }
+template <typename T>
+inline T __shfl_xor(T v, int mask, int = 64) { return sm_emu_exchange(v, sm_emu::lane() ^ mask); }
 // v_mov_b32_dpp with bank mask 0xf and bound_ctrl off, for the three controls of the wave scans (fastpath_dev.h):
 // row_shr:n (0x111 .. 0x11f; lane l - n of the same 16-lane row, none for the row's first n lanes), row_bcast:15
 // (0x142; lane 15 of the row before, none for row 0) and row_bcast:31 (0x143; lane 31, for rows 2 and 3). A lane
@@ -133,6 +135,12 @@ inline unsigned long long atomicCAS(unsigned long long* p, unsigned long long cm
 }
 inline unsigned long long atomicMax(unsigned long long* p, unsigned long long v) {
   unsigned long long o = __atomic_load_n(p, __ATOMIC_SEQ_CST);
+  while (v > o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {
+  }
+  return o;
+}
+inline unsigned atomicMax(unsigned* p, unsigned v) {
+  unsigned o = __atomic_load_n(p, __ATOMIC_SEQ_CST);
   while (v > o && !__atomic_compare_exchange_n(p, &o, v, false, __ATOMIC_SEQ_CST, __ATOMIC_SEQ_CST)) {
   }
   return o;

@@ -513,12 +513,14 @@ def test_spilled_stacks_carried_into_key_range(stack):
 
 
 def _run_unkeyed(text, cols, ts, ranges, ordinals=None):
-    """run_stream for the unkeyed walk with phase timing on: the pairs, and whether the j-tile kernel ran."""
+    """run_stream for the unkeyed walk with phase timing on: the pairs, how often the j-tile kernel ran, and per batch
+    what ordered its pairs: {n: events, j_count, j_tile: launches of the two tile kernels, lsd: launches of the LSD
+    j passes (up-sweeps and scatters)}. A batch whose tile placement raised its error word has both j_tile and lsd."""
     import torch
     from siddhi_amd.testing import ProductApp
     app = ProductApp(text, fast_stack=2, fast_timing=1)
     dev = torch.device("cuda", 0)
-    got, tiled = [], 0
+    got, tiled, stats = [], 0, []
     for lo, hi in ranges:
         tcols = [torch.from_numpy(np.ascontiguousarray(c[lo:hi])).to(dev) for c in cols]
         tts = torch.from_numpy(np.ascontiguousarray(ts[lo:hi], dtype=np.int64)).to(dev)
@@ -526,19 +528,48 @@ def _run_unkeyed(text, cols, ts, ranges, ordinals=None):
         base = lo if ordinals is None else 0
         torch.cuda.synchronize()
         app.process_device_batch("StockStream", tts, tcols, ordinals=tord, ordinal_base=base)
-        tiled += int(app.get_stat("kernel_calls:j_tile"))
+        calls = {k: int(app.get_stat("kernel_calls:" + k))
+                 for k in ("j_count", "j_tile", "j_up", "j_pass", "j_pass_last")}
+        tiled += calls["j_tile"]
+        stats.append(dict(n=hi - lo, j_count=calls["j_count"], j_tile=calls["j_tile"],
+                          lsd=calls["j_up"] + calls["j_pass"] + calls["j_pass_last"]))
         got.append(app.device_matches_host("q").view(np.int32).astype(np.int64) + base)
     app.close()
-    return np.concatenate(got), tiled
+    return np.concatenate(got), tiled, stats
 
 
-@pytest.mark.parametrize("case", ["spikes", "sharded", "window_8s_spikes", "long_wait", "no_within"])
+def _falling_run(n, start, L):
+    """Price 10 everywhere (neither an e1 nor above one), but L falling prices from `start` on, all pending until the
+    one price of 1000 behind them completes them: L pairs on one e2."""
+    price = np.full(n, 10.0)
+    price[start:start + L] = np.linspace(59.0, 21.5, L)
+    price[start + L] = 1000.0
+    return price
+
+
+def _unkeyed_cols(price, seed=3):
+    n = len(price)
+    rng = np.random.default_rng(seed)
+    tsa = np.arange(n, dtype=np.int64)
+    return [rng.integers(0, 10, n).astype(np.int32), price, rng.integers(0, 2000, n).astype(np.int64), tsa], tsa
+
+
+@pytest.mark.parametrize("case", ["spikes", "sharded", "window_8s_spikes", "window_8s_falling", "long_wait",
+                                  "no_within"])
 def test_unpartitioned_j_tile_order(case, monkeypatch):
-    """Round 6: the unkeyed walk's (e1, e2) pairs put in e2 order by output tiles of 2048 ordinals (fastpath3.hip
+    """Round 6: the unkeyed walk's (e1, e2) pairs put in e2 order by output tiles of 2048 ordinals (jtile_dev.h
     jt_place_kernel) when no match lies more than 8192 ordinals after its e1; otherwise, or when a tile holds more
-    than 4096 pairs, by the LSD j passes. Both equal the oracle: price spikes that complete hundreds to thousands of
-    partials at one e2 (ties of j, i ascending), sharded ordinals with gaps, ragged batches with carried partials, and
-    windows past the tile path's reach."""
+    than 4096 pairs, by the LSD j passes. Both equal the oracle: price spikes (ties of j, i ascending), sharded
+    ordinals with gaps, ragged batches with carried partials, and windows past the tile path's reach. The per-batch
+    launch counts say which path produced the output: the j_tile mark alone is recorded before the placement's error
+    word is read, so a batch the tile path produced has j_tile == 1 and no LSD pass.
+
+    What is pending in this unkeyed pattern never rises from oldest to newest (an event completes every pending e1
+    below it), so a spike over random prices completes about a dozen partials, not thousands: `window_8s_spikes` has
+    at most 14 pairs on one e2, at most 2054 per tile and a largest e2 - e1 of 6982 (computed from the stream), and
+    the tile path produces every batch. `window_8s_falling` is the stream that does what that case was meant to: a
+    falling run of 7000 prices completed by one e2 (7000 pairs and a few on one j, e2 - e1 < 8000), a tile over the
+    4096-pair cap, so the placement refuses and the LSD passes take that batch."""
     n = 60000
     rng = np.random.default_rng(11)
     price = rng.uniform(21.0, 60.0, n)
@@ -547,7 +578,11 @@ def test_unpartitioned_j_tile_order(case, monkeypatch):
         price[rng.integers(0, n, n // 300)] = 1000.0  # each spike completes every pending partial of the last second
     if case == "window_8s_spikes":
         within = " within 8 sec"
-        price[np.arange(7000, n, 7000)] = 1000.0  # ~7000 partials per spike: more than a tile's workgroup holds
+        price[np.arange(7000, n, 7000)] = 1000.0
+    if case == "window_8s_falling":
+        within = " within 8 sec"
+        price[30000:37000] = np.linspace(59.0, 21.5, 7000)
+        price[37000] = 1000.0
     if case == "long_wait":  # a falling run of 10000 events, then a spike: a match 10000 ordinals after its e1
         within = " within 30 sec"
         price[20000:30000] = np.linspace(59.0, 21.5, 10000)
@@ -565,13 +600,87 @@ def test_unpartitioned_j_tile_order(case, monkeypatch):
         ordinals = 3 * np.arange(n, dtype=np.int64) + 1
         exp = 3 * exp + 1
     ranges = [(0, n)] if case == "long_wait" else pieces(n, [1, 8191, 20000])
-    got, tiled = _run_unkeyed(text, cols, tsa, ranges, ordinals)
+    got, tiled, stats = _run_unkeyed(text, cols, tsa, ranges, ordinals)
+    print(case, stats)
     np.testing.assert_array_equal(got, exp)
     if case in ("spikes", "sharded"):
         assert tiled > 0
+    if case in ("spikes", "sharded", "window_8s_spikes"):
+        assert len(stats) == 4
+        for b in stats:
+            assert (b["j_tile"], b["lsd"]) == ((1, 0) if b["n"] > 1 else (0, 0)), stats
+    if case == "window_8s_falling":
+        assert 7000 <= np.bincount(exp[:, 1]).max() < 7100  # the run, and what was pending above it
+        assert any(b["j_tile"] == 1 and b["lsd"] > 0 for b in stats), stats  # the refusal really ran
     if case == "long_wait":
         assert tiled == 0
+        assert stats[0]["j_count"] == 1 and stats[0]["lsd"] > 0, stats
     monkeypatch.setenv("SM_JTILE", "0")
-    lsd, tiled0 = _run_unkeyed(text, cols, tsa, ranges, ordinals)
+    lsd, tiled0, stats0 = _run_unkeyed(text, cols, tsa, ranges, ordinals)
     assert tiled0 == 0
+    assert all(b["j_count"] == 0 and b["lsd"] > 0 for b in stats0 if b["n"] > 1), stats0
     np.testing.assert_array_equal(lsd, exp)
+
+
+def _spikes_20000():
+    rng = np.random.default_rng(11)
+    price = rng.uniform(21.0, 60.0, 20000)
+    price[rng.integers(0, 20000, 20000 // 300)] = 1000.0
+    return price
+
+
+_offset_ref = {}
+
+
+@pytest.mark.parametrize("o0", [1, 2048, 5 * 2048 + 7])
+def test_unpartitioned_j_tile_offset_ordinals(o0):
+    """Contiguous ordinals from o0 > 0 with ordinal base 0 (a later batch fed with absolute ordinals): the i-tiles
+    below the batch's first ordinal belong to the count kernel's chunk 0. Both batches are ordered by the tile path;
+    the second one runs on scratch the first left behind. (The arena cannot be poisoned from here: the deterministic
+    statement of this is tests/test_jtile_emu.py::test_first_ordinal_above_base.)"""
+    cols, tsa = _unkeyed_cols(_spikes_20000())
+    text = app_text(partitioned=False)
+    if "exp" not in _offset_ref:
+        _offset_ref["exp"] = oracle_pairs(text, cols, tsa)
+    exp = _offset_ref["exp"] + o0
+    got, _, stats = _run_unkeyed(text, cols, tsa, [(0, 12000), (12000, 20000)], tsa + o0)
+    print(o0, stats)
+    np.testing.assert_array_equal(got, exp)
+    assert [(b["j_tile"], b["lsd"]) for b in stats] == [(1, 0), (1, 0)], stats
+
+
+@pytest.mark.parametrize("L", [4096, 4097])
+def test_unpartitioned_j_tile_capacity(L):
+    """L pairs on one e2 (no `within`, one batch of 12288 events): 4096 is what a tile's workgroup holds and the tile
+    path produces the output; with 4097 the placement runs, refuses (error bit 1), and the LSD passes produce it."""
+    cols, tsa = _unkeyed_cols(_falling_run(12288, 3000, L))
+    text = app_text(partitioned=False, within="")
+    exp = oracle_pairs(text, cols, tsa)
+    assert len(exp) == L and (exp[:, 1] == 3000 + L).all() and (np.diff(exp[:, 0]) == 1).all()
+    got, _, stats = _run_unkeyed(text, cols, tsa, [(0, len(tsa))])
+    print(L, stats)
+    np.testing.assert_array_equal(got, exp)
+    assert stats[0]["j_tile"] == 1
+    assert stats[0]["lsd"] == 0 if L == 4096 else stats[0]["lsd"] > 0, stats
+
+
+@pytest.mark.parametrize("d", [8192, 8193])
+def test_unpartitioned_j_tile_reach(d):
+    """One pair whose e2 is d ordinals after its e1 (`within 30 sec`, one event per ms): 8192 is the tile path's reach;
+    at 8193 the count kernel reports it, no placement is launched, and the LSD passes produce the output."""
+    price = np.full(14000, 10.0)
+    price[1000] = 50.0
+    price[1000 + d] = 1000.0
+    cols, tsa = _unkeyed_cols(price)
+    text = app_text(partitioned=False, within=" within 30 sec")
+    exp = oracle_pairs(text, cols, tsa)
+    np.testing.assert_array_equal(exp, [[1000, 1000 + d]])
+    got, _, stats = _run_unkeyed(text, cols, tsa, [(0, len(tsa))])
+    print(d, stats)
+    np.testing.assert_array_equal(got, exp)
+    b = stats[0]
+    assert b["j_count"] == 1
+    if d == 8192:
+        assert (b["j_tile"], b["lsd"]) == (1, 0), stats
+    else:
+        assert b["j_tile"] == 0 and b["lsd"] > 0, stats
