@@ -81,6 +81,10 @@ struct FastCarry {
   int64_t* parts = nullptr;  // device, pn rows of pw words
   int64_t pn = 0, pcap = 0;
   int pw = 0;               // k + 1
+  // second buffer of `rows` (spare_words words): the carry-out that writes each row once, in its place, writes there
+  // while it reads the old rows, and the two change places (stack.hip build_carry_runs)
+  int64_t* spare = nullptr;
+  int64_t spare_words = 0;
   void reserve(int64_t rows_needed, int w);
   void reserve_parts(int64_t rows_needed, int w, hipStream_t s);  // the old rows are not kept
   void release();

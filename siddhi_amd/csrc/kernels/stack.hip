@@ -720,14 +720,10 @@ __global__ void __launch_bounds__(kOB) stage_base_kernel(const uint32_t* __restr
 }
 
 // ---- carry out
-__global__ void carry_rows_kernel(const int64_t* __restrict__ cand, int64_t n, const NfaStream* __restrict__ st,
-                                  int nattr, const int64_t* __restrict__ old, int w, int64_t kmin, int key_bits,
-                                  int64_t* __restrict__ rows, uint64_t* __restrict__ kord, uint64_t* __restrict__ kkey,
-                                  uint32_t* __restrict__ idx, const int32_t* __restrict__ sid) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int64_t* c = cand + 4 * i;
-  int64_t* r = rows + i * w;
+// the carry row of candidate c = [key, ordinal, ts, batch row | -(carried row) - 1]
+__device__ __forceinline__ void carry_row(const int64_t* __restrict__ c, const NfaStream* __restrict__ st, int nattr,
+                                          const int64_t* __restrict__ old, int w, int64_t* __restrict__ r,
+                                          const int32_t* __restrict__ sid) {
   if (c[3] >= 0) {
     r[0] = c[0];
     r[1] = c[1];
@@ -738,6 +734,16 @@ __global__ void carry_rows_kernel(const int64_t* __restrict__ cand, int64_t n, c
     const int64_t* o = old + (-c[3] - 1) * w;
     for (int k = 0; k < w; ++k) r[k] = o[k];
   }
+}
+
+__global__ void carry_rows_kernel(const int64_t* __restrict__ cand, int64_t n, const NfaStream* __restrict__ st,
+                                  int nattr, const int64_t* __restrict__ old, int w, int64_t kmin, int key_bits,
+                                  int64_t* __restrict__ rows, uint64_t* __restrict__ kord, uint64_t* __restrict__ kkey,
+                                  uint32_t* __restrict__ idx, const int32_t* __restrict__ sid) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t* c = cand + 4 * i;
+  carry_row(c, st, nattr, old, w, rows + i * w, sid);
   kord[i] = (uint64_t)c[1] ^ 0x8000000000000000ull;
   kkey[i] = key_bits < 64 ? (uint64_t)(c[0] - kmin) : (uint64_t)c[0] ^ 0x8000000000000000ull;
   idx[i] = (uint32_t)i;
@@ -755,6 +761,41 @@ __global__ void gather_rows_kernel(const int64_t* __restrict__ src, const uint32
   if (i >= n) return;
   const int64_t* s = src + (int64_t)idx[i] * w;
   for (int k = 0; k < w; ++k) dst[i * w + k] = s[k];
+}
+
+// Carry-out without a sort (ring kernel, every candidate written by it): the ring kernel leaves each key's run of
+// candidates {first, length} in ktab, bucket-major [d][h], and a key's rows follow those of every smaller key
+// kr = h << kRB | d, so a row's place is a prefix sum of the lengths in key order. Workgroup h, thread d: key kr.
+// carry_scan_kernel: the prefix inside the workgroup's kBins keys and the workgroup's total.
+static_assert(kBins == kOB, "one thread per bucket");
+__global__ void __launch_bounds__(kOB) carry_scan_kernel(const uint2* __restrict__ ktab, uint4* __restrict__ krun,
+                                                         uint32_t* __restrict__ btot) {
+  __shared__ uint32_t lw[kOB / 64];
+  const int h = blockIdx.x, d = threadIdx.x;
+  const uint2 e = ktab[(int64_t)d * kKeys + h];
+  uint32_t tot;
+  const uint32_t r = block_excl(e.y, lw, &tot);
+  krun[((int64_t)h << kRB) | d] = make_uint4(e.x, e.y, r, 0u);  // key order: the placement reads it coalesced
+  if (d == 0) btot[h] = tot;
+}
+
+// carry_place_kernel: the rows before the workgroup's keys (the totals of the workgroups before it), then each key's
+// rows, oldest first as the ring kernel wrote its candidates: neighbouring threads write neighbouring rows. Out of
+// place: `rows` is not the buffer `old` points into.
+__global__ void __launch_bounds__(kOB) carry_place_kernel(const uint4* __restrict__ krun,
+                                                          const uint32_t* __restrict__ btot,
+                                                          const int64_t* __restrict__ cand, int64_t n,
+                                                          const NfaStream* __restrict__ st, int nattr,
+                                                          const int64_t* __restrict__ old, int w,
+                                                          int64_t* __restrict__ rows) {
+  __shared__ uint32_t lw[kOB / 64];
+  const int h = blockIdx.x, d = threadIdx.x;
+  uint32_t before;
+  (void)block_excl(d < h ? btot[d] : 0u, lw, &before);
+  const uint4 e = krun[((int64_t)h << kRB) | d];
+  const int64_t r0 = (int64_t)before + e.z;
+  for (uint32_t j = 0; j < e.y; ++j)
+    if (r0 + j < n) carry_row(cand + 4 * ((int64_t)e.x + j), st, nattr, old, w, rows + (r0 + j) * w, nullptr);
 }
 
 inline dim3 grid_of(int64_t n, int t = 256) { return dim3((unsigned)std::max<int64_t>(1, (n + t - 1) / t)); }
@@ -791,6 +832,9 @@ void FastCarry::reserve_parts(int64_t rows_needed, int w, hipStream_t s) {
 
 void FastCarry::release() {
   if (rows) (void)hipFree(rows);
+  if (spare) (void)hipFree(spare);
+  spare = nullptr;
+  spare_words = 0;
   if (parts) (void)hipFree(parts);
   rows = parts = nullptr;
   cap = n = 0;
@@ -831,6 +875,38 @@ void build_carry(const int64_t* cand, int64_t ncand, const NfaStream* st, int na
   carry.reserve(ncand, w);
   hipLaunchKernelGGL(gather_rows_kernel, grid_of(ncand), dim3(256), 0, s, rows, fin, ncand, w, carry.rows);
   SM_HIP(hipStreamSynchronize(s));
+  carry.n = ncand;
+  sc.used = mark;
+}
+
+// The carry of the ring kernel's candidates placed by key without a sort (carry_scan_kernel): written once, into the
+// carry's second buffer (a candidate that is a carried partial copies its old row), which then becomes `rows`.
+static void build_carry_runs(const uint2* ktab, int H, const int64_t* cand, int64_t ncand, const NfaStream* st,
+                             int nattr, FastCarry& carry, Scratch& sc, hipStream_t s) {
+  const int w = 3 + nattr;
+  if (ncand == 0) {
+    carry.n = 0;
+    carry.width = w;
+    return;
+  }
+  const size_t mark = sc.used;
+  uint4* krun = (uint4*)sc.take(((size_t)H << kRB) * 16);
+  uint32_t* btot = (uint32_t*)sc.take((size_t)H * 4);
+  if (ncand * w > carry.spare_words) {
+    if (carry.spare) SM_HIP(hipFree(carry.spare));
+    carry.spare = nullptr;
+    carry.spare_words = std::max<int64_t>(ncand * w, std::max<int64_t>(carry.spare_words * 2, 4096));
+    SM_HIP(hipMalloc(&carry.spare, (size_t)carry.spare_words * 8));
+  }
+  hipLaunchKernelGGL(carry_scan_kernel, dim3(H), dim3(kOB), 0, s, ktab, krun, btot);
+  hipLaunchKernelGGL(carry_place_kernel, dim3(H), dim3(kOB), 0, s, krun, btot, cand, ncand, st, nattr,
+                     (const int64_t*)carry.rows, w, carry.spare);
+  SM_HIP(hipStreamSynchronize(s));
+  const int64_t old_words = carry.cap * carry.width;
+  std::swap(carry.rows, carry.spare);
+  carry.cap = carry.spare_words / w;
+  carry.spare_words = old_words;
+  carry.width = w;
   carry.n = ncand;
   sc.used = mark;
 }
@@ -924,6 +1000,7 @@ int64_t stack_pipeline(const StackPlan& p, const FastArgs& a, const FastHostInfo
   // gathered records and scattered pop slots with little locality, 54.6 + 35 ms against 31.7 + 6.7 ms.)
   static const bool v2 = getenv("SM_STACK_V2") && atoi(getenv("SM_STACK_V2")) != 0;
   int64_t M = 0;
+  uint2* ktab = nullptr;  // the ring kernel's run per key, for the carry-out
   {
     sa.sbase = sbase;
     sa.stage = (uint64_t*)sc.take((size_t)(n + extra) * 8);
@@ -979,6 +1056,7 @@ int64_t stack_pipeline(const StackPlan& p, const FastArgs& a, const FastHostInfo
       c4.cand = sa.cand;
       c4.cand_n = sa.cand_n;
       c4.cand_cap = sa.cand_cap;
+      c4.ktab = ktab = (uint2*)sc.take((size_t)kBins * kKeys * 8);
       Stack4Cold* c4d = (Stack4Cold*)sc.take(sizeof(Stack4Cold));
       SM_HIP(hipMemcpyAsync(c4d, &c4, sizeof(c4), hipMemcpyHostToDevice, s));
       SM_HIP(hipStreamSynchronize(s));  // c4 is a local of this block
@@ -1094,7 +1172,14 @@ int64_t stack_pipeline(const StackPlan& p, const FastArgs& a, const FastHostInfo
   // carried partials appended before it, one key sort of span bits orders the carry
   int kb = 1;
   while (kb < 63 && ((((int64_t)p.H << kRB) - 1) >> kb) != 0) ++kb;
-  if (ncand_in == 0) build_carry(sa.cand, ncand, a.st, hi.nattr, carry, sc, s, kb, p.kmin, true);
+  // ... or, after the ring kernel, none: the rows' places are a scan of the keys' run lengths (SM_CARRY_SORT=1, read
+  // per call, keeps the sort: A/B and the tests that compare the two routes in one process)
+  const char* cse = getenv("SM_CARRY_SORT");
+  const bool by_scan = ncand_in == 0 && ktab && !(cse && atoi(cse) != 0);
+  if (by_scan) tmark("carry_by_scan");  // (an empty interval: which route ran, for kernel_calls:carry_by_scan)
+  if (by_scan)
+    build_carry_runs(ktab, p.H, sa.cand, ncand, a.st, hi.nattr, carry, sc, s);
+  else if (ncand_in == 0) build_carry(sa.cand, ncand, a.st, hi.nattr, carry, sc, s, kb, p.kmin, true);
   else build_carry(sa.cand, ncand, a.st, hi.nattr, carry, sc, s);
   tmark("carry_out");
   SM_HIP(hipStreamSynchronize(s));

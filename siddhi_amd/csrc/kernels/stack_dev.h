@@ -239,6 +239,7 @@ struct Stack4Cold {
   int64_t* cand;
   uint32_t* cand_n;
   uint32_t cand_cap;
+  uint2* ktab;  // per key, bucket-major [d][h]: {its run's first candidate, its length}; or nullptr (stack.hip, carry-out)
 };
 
 #ifndef SM_EXACT4_INLINE
@@ -684,10 +685,14 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
         // A tie of inexact codes and a spill onto a full ring take the general step below.
         int nhit = 0, nexp = 0;
         bool anytie = false;
+        // expired: jt - t > weff, as one threshold for the kC compares (event times are in [0, 2^30), entry times at
+        // least -2^30, padding 2^30 and weff at most 2^31 - 1: neither side wraps; a lane without an event may hold
+        // any time, hence the unsigned difference)
+        const int32_t tmin = (int32_t)((uint32_t)jt - (uint32_t)weff);
 #pragma unroll
         for (int u = 0; u < kC; ++u) {
           nhit += cmp_fixed<OP>(cj, st.c[u]) ? 1 : 0;
-          nexp += jt - st.t[u] > weff ? 1 : 0;
+          nexp += st.t[u] < tmin ? 1 : 0;
           anytie |= st.c[u] == cj;
         }
         const int nl = st.n - nexp;
@@ -937,6 +942,9 @@ __global__ void __launch_bounds__(kT4) stack4_kernel(Stack4Args a) {
     const Stack4Cold* c4 = a.cold;
     if (lane == 63 && inc) base = atomicAdd(c4->cand_n, inc);
     base = __shfl(base, 63, 64) + inc - keep;
+    // the key's run, for the carry-out that places rows by a scan of these counts instead of a sort (a wave's keys are
+    // consecutive words of bucket d's row)
+    if (has && c4->ktab) c4->ktab[(int64_t)d * kKeys + h] = make_uint2(base, keep);
     if (keep) {
       const ExactSrc ex{c4->exact_codes, c4->vtype, c4->vattr, c4->cwidth, c4->vcol, c4->ord, c4->obase, c4->n,
                         c4->crow, c4->o0, cs, ce};

@@ -2643,11 +2643,11 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
     const CompiledQuery& cq = qp->cq;
     if (std::find(cq.streams.begin(), cq.streams.end(), s) == cq.streams.end()) continue;
     // patterns: records / staging / pairs (64 B per event), carry-out candidates (32 B each) and the carried
-    // partials' working arrays, plus the bucket-stack spill rings and bounded buffers
+    // partials' working arrays, plus the bucket-stack spill rings, its per-key run tables and bounded buffers
     const size_t nc = (size_t)qp->carry.n, wc = (size_t)std::max(qp->carry.width, 4);
     need = std::max(need, cq.hdr.kind == 0 ? n / 8 + n / 1024 + (64 << 20)
                                            : n * 68 + std::min<size_t>(n + nc, (size_t)1 << 26) * 32 +
-                                                 nc * (160 + 8 * wc) + ((size_t)640 << 20));
+                                                 nc * (160 + 8 * wc) + ((size_t)672 << 20));
     // sequences (seqpath.hip): sort pairs, links, dense ids (40 B per event), candidates (32 B per event and carried
     // row) and the carry build's rows and sort arrays for up to 2^24 keys with events plus the carried ones (a batch
     // with more distinct keys than fit is refused by the kernels' host entry before anything changes)

@@ -44,7 +44,8 @@ FAMILIES = [("walk_kernel<", "walk"), ("jt_count_kernel", "j_count"), ("jt_place
 
 # the closed-form pipelines (configs 3 / 4) use the radix sort only to order the carried partials
 CARRY_FAMILIES = [("rs_downsweep", "carry_out"), ("rs_upsweep", "carry_out"), ("carry_rows_kernel", "carry_out"),
-                  ("gather_u64_kernel", "carry_out"), ("gather_rows_kernel", "carry_out")]
+                  ("gather_u64_kernel", "carry_out"), ("gather_rows_kernel", "carry_out"),
+                  ("carry_scan_kernel", "carry_out"), ("carry_place_kernel", "carry_out")]
 
 
 def family(name, config=4):
