@@ -222,6 +222,14 @@ int sm_app_process_device_batch(sm_app* app, const char* stream_id, size_t n, co
  * event lies inside T; one B event may complete many, oldest e1 first. It carries the e1 events still open at the end
  * of the batch, leaves the (e1, e2) pairs on the device in the reference's order and hands over to the NFA kernel as
  * the sequence does, its carried e1 events replayed first. The same pattern without a `within` runs on the NFA kernel.
+ * The timeout `every e1=A[c1] -> not B[c2] for W` of an @app:playback app (B of A's schema or A itself, c2 reading the B
+ * event and constants only, the select reading e1 only, no within, no having; partitioned: each read stream keyed by
+ * one INT / LONG attribute of its own) runs a closed form too under the same conditions ("fast_path:<query>" = 11,
+ * "match_arity:<query>" = 1: sm_app_device_matches gives e1's ordinals): every A event passing c1 comes out with
+ * timestamp ts + W at the first row of the feed, heartbeats and rows of other streams included, whose playback clock
+ * reaches that time, unless a B event of its partition instance passing c2 arrives before. Unlike the other closed
+ * forms it advances the playback clock. It carries the e1 events still waiting and hands over to the NFA kernel as the
+ * pattern does, also when a row of a read stream lies below the clock.
  * "output_events:<query>" (sm_app_get_stat) = output events of the last such batch; "nfa_kernel:<query>" = which NFA
  * kernel ran it (1 = query-specialised, 2 = interpreter, 0 = none yet). */
 int sm_app_process_device_events(sm_app* app, size_t n, const int32_t* d_stream_idx, const int64_t* d_timestamps,

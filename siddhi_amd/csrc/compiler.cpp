@@ -927,6 +927,54 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
         }
       }
     }
+    // ---- the timeout: every e1=A[c1] -> not B[c2] for W, B of A's schema or A itself (kernels/absent_dev.h). c2 reads
+    // the B event and constants only: a cancelling row then cancels every pending partial of its key, so the processor's
+    // lastArrivalTime gate never meets a live partial. The select reads e1 only (there is no other event in an output)
+    if (q.input == InputKind::PATTERN && root_el->kind == StateKind::NEXT && !root_el->has_within && !q.having &&
+        root_el->a->kind == StateKind::EVERY && root_el->a->a->kind == StateKind::STREAM && !root_el->a->has_within &&
+        !root_el->a->a->has_within && root_el->b->kind == StateKind::ABSENT && root_el->b->has_wait &&
+        root_el->b->wait_ms >= 1 && !root_el->b->has_within && (int)pres.size() == 2 && app.playback) {
+      bool ok = pres[0].kind == PK_STREAM && pres[1].kind == PK_ABSENT_STREAM && pres[0].stateId == 0 &&
+                pres[1].stateId == 1 && withins.empty();
+      for (size_t r = 0; ok && r < refs.size(); r += 2)
+        if (refs[r] != 0 || !(refs[r + 1] == 0 || refs[r + 1] == kCurrent)) ok = false;
+      for (int i = 0; ok && i < pres[1].progLen; ++i) {
+        const Instr& in = code[pres[1].progOff + i];
+        if (in.op == OP_TS || in.op == OP_COL) ok = false;
+        if (in.op == OP_VAR && (in.a != 1 || !(in.b == 0 || in.b == kCurrent))) ok = false;
+      }
+      const int sa = ok ? lw.metas[0].stream : -1;
+      const int sb = ok ? stream_index(app, root_el->b->stream_id) : -1;
+      std::vector<int> keycol(app.streams.size(), -1);
+      for (int m = 0; ok && m < 2; ++m) {
+        const StreamDef& d0 = app.streams[sa];
+        const StreamDef& d = app.streams[m == 0 ? sa : sb];
+        ok = d.attrs.size() == d0.attrs.size();
+        for (size_t c = 0; ok && c < d.attrs.size(); ++c) ok = d.attrs[c].type == d0.attrs[c].type;
+        if (!ok || partition < 0) continue;
+        // partitioned: each read stream keyed by one INT / LONG attribute of its own
+        ok = false;
+        for (auto& w : app.partitions[partition].with)
+          if (w.stream_id == d.id && w.key->kind == ExprKind::VAR && w.key->stream_ref.empty()) {
+            const int c = d.index_of(w.key->attr);
+            if (c >= 0 && (d.attrs[c].type == AttrType::INT || d.attrs[c].type == AttrType::LONG)) {
+              keycol[m == 0 ? sa : sb] = c;
+              ok = true;
+            }
+          }
+      }
+      if (ok) {
+        cq.fast_absent = true;
+        cq.fast_abs_keycol = keycol;
+        cq.fast_abs_wait = root_el->b->wait_ms;
+        cq.fast_abs_stream[0] = sa;
+        cq.fast_abs_stream[1] = sb;
+        for (int m = 0; m < 2; ++m) {
+          cq.fast_abs_off[m] = pres[m].progOff;
+          cq.fast_abs_len[m] = pres[m].progLen;
+        }
+      }
+    }
   }
   h.npre = (int)pres.size();
   h.npost = (int)posts.size();
@@ -941,6 +989,7 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
   for (int m = 0; m < cq.fast_seq_k; ++m) refs.insert(refs.end(), {m, 0});  // hidden (e1, ..., ek) ordinals, likewise
   for (int m = 0; m < cq.fast_seq_ms; ++m) refs.insert(refs.end(), {m, 0});
   for (int m = 0; m < cq.fast_pat_k; ++m) refs.insert(refs.end(), {m, 0});
+  if (cq.fast_absent) refs.insert(refs.end(), {0, 0});  // hidden e1 ordinal, likewise
   h.nrefs = (int)refs.size() / 2;
   h.nconst = (int)consts.size();
   // per-key state layout (int64 words)

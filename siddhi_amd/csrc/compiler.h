@@ -84,9 +84,23 @@ struct CompiledQuery {
   int fast_patk_off[8] = {0}, fast_patk_len[8] = {0};
   int64_t fast_patk_within[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
   std::vector<int> fast_patk_keycol;
-  // uint32 words per device match tuple: k, 2 for every other state query, 1 for a filter (its kept row)
+  // fast path: every e1=A[c1] -> not B[c2] for W, B a stream of A's schema or A itself, c2 reading the B event and
+  // constants only, the select reading e1 only, no within, no having, @app:playback (pattern: every A event passing c1
+  // is emitted with timestamp ts + W once the playback clock reaches it, unless a B event of its partition instance
+  // passing c2 arrives before; kernels/absent_dev.h). A mark of its own: such a query runs through the interleaved
+  // entry point only. fast_abs_stream = the app streams of A and B, fast_abs_off / len = c1 and c2 (state context, c2
+  // over slot 1 alone), fast_abs_wait = W >= 1 ms, fast_abs_keycol[s] as fast_ms_keycol. The plan carries one hidden
+  // ordinal ref, e1's, after the visible ones.
+  bool fast_absent = false;
+  int fast_abs_stream[2] = {0, 0};
+  int fast_abs_off[2] = {0, 0}, fast_abs_len[2] = {0, 0};
+  int64_t fast_abs_wait = 0;
+  std::vector<int> fast_abs_keycol;
+  // uint32 words per device match tuple: k, 2 for every other state query, 1 for a filter (its kept row) and for the
+  // timeout (its e1)
   int match_arity() const {
-    return hdr.kind == 0 ? 1 : fast_seq_k ? fast_seq_k : fast_seq_ms ? fast_seq_ms : fast_pat_k ? fast_pat_k : 2;
+    return hdr.kind == 0 || fast_absent ? 1
+           : fast_seq_k ? fast_seq_k : fast_seq_ms ? fast_seq_ms : fast_pat_k ? fast_pat_k : 2;
   }
 };
 

@@ -1,6 +1,8 @@
 // Host entry of the closed-form `every e1 -> e2 within T` kernels (fastpath.hip: general form;
 // fastpath3.hip: keyed bandwidth form for single-column keys and a single compared attribute).
 #pragma once
+#include <functional>
+
 #include "nfa.h"
 #include "primitives.h"
 #include "stream_ops.h"
@@ -44,7 +46,7 @@ struct FastState {
   int walk_wgs_per_cu = 0;  // resident walk workgroups per CU
   // pipeline of the last batch: 2 = sort / walk, 3 = bucket stack; seqpath.hip: 6 = adjacent pairs, 7 = adjacent runs,
   // 8 = adjacent runs over several streams, 9 = the pattern over two streams, 10 = the k-state pattern over several
-  // streams
+  // streams, 11 = the timeout `every A -> not B for W`
   int last_path = 0;
 };
 
@@ -193,6 +195,47 @@ struct MPatKPlan : MSeqKeys {
 // carry.ts_last. Every error result is returned before the carry or tuples_out is touched. Sets fs.last_path = 10.
 int64_t fast_pat_k(const FastArgs& a, const int32_t* sid, const MPatKPlan& p, int nattr, FastState& fs, FastCarry& carry,
                    uint32_t* tuples_out, int64_t tuples_cap, Scratch& sc, hipStream_t s, FastTimings* tm = nullptr);
+
+// The timeout `every e1=A[c1] -> not B[c2] for W` over one or two streams of one schema on an interleaved batch
+// (seqpath.hip, absent_dev.h has the rule and the kernels).
+struct AbsentPlan : MSeqKeys {
+  int stream[2] = {0, 0};          // app stream of A and of B (may be equal)
+  int off[2] = {0, 0}, len[2] = {0, 0};  // c1 (over e1) and c2 (over the B event alone)
+  int64_t wait = 0;                // W >= 1
+};
+
+// Every partition instance the query has created, with the global ordinal of the row that created it: [key, ordinal]
+// rows sorted by key (device). It lives with the carry and orders the outputs of instances that are due at one position.
+struct AbsentInst {
+  int64_t* rows = nullptr;
+  int64_t n = 0, cap = 0;
+  void reserve(int64_t rows_needed);  // the old rows are not kept
+  void release();
+};
+
+// The m outputs of a batch, in the reference's order (device): e1's ordinal relative to a.ordinal_base (a carried one
+// negative as int32), the select values (m x nsel), the timestamp ts[e1] + W, the trigger position p in the batch and
+// the instance's creation ordinal (-1: unpartitioned).
+struct AbsentOut {
+  uint32_t* e1;
+  DVal* vals;
+  int64_t* ts;
+  int64_t* pos;
+  int64_t* create;
+};
+
+// a.st, `sid`, key_remap and FAST_KEY_SPAN as fast_seq_ms. clk: the playback clock at every row of the batch
+// (build_event_index's ev_clock). blob_dev: the query's device plan (its select programs). `out` is called once, with
+// the number of outputs, when nothing has been changed yet, and returns where they go. The carry holds the open
+// partials' e1 rows as fast_pat_ms's, `inst` the instances. FAST_NON_MONOTONE: a row of a read stream lies below the
+// clock. Every error result is returned before the carry, `inst` or an output is touched. Sets fs.last_path = 11.
+int64_t fast_absent(const FastArgs& a, const int32_t* sid, const int64_t* clk, const AbsentPlan& p, int nattr,
+                    const char* blob_dev, FastState& fs, FastCarry& carry, AbsentInst& inst,
+                    const std::function<AbsentOut(int64_t)>& out, Scratch& sc, hipStream_t s, FastTimings* tm = nullptr);
+
+// The hand-over of the instances to the NFA kernel: word `word` of the per-key state of slots 0 .. n - 1 (ks: word-major,
+// one column of state_slots per word) becomes create[slot], the instance's creation ordinal.
+void absent_set_creation(int64_t* ks, int64_t state_slots, int word, const int64_t* create, int64_t n, hipStream_t s);
 
 // keys[i] = the partition key of row i (the key column of its own stream, as int64), 0 for a row that is not read: the
 // one key column remap_keys takes when an interleaved batch's keys become dense ids

@@ -1,5 +1,5 @@
-// Host entries of the five sequence closed forms (fastpath.h has their contracts, seq_dev.h / mseq_dev.h / mpat_dev.h /
-// mpatk_dev.h the rules and the kernels). Every driver runs one batch through the same stages, each written once below:
+// Host entries of the six sequence closed forms (fastpath.h has their contracts, seq_dev.h / mseq_dev.h / mpat_dev.h /
+// mpatk_dev.h / absent_dev.h the rules and the kernels). Every driver runs one batch through the same stages, each written once below:
 //   begin      Batch: the timing start, the scratch mark, and leave(), which every return goes through
 //   facts      one streaming pass over the keys, event times and ordinals, plus the carried ordinals; its read-back is
 //              the only host round trip before anything is changed (Facts: the same fields for SeqFacts and MSeqFacts)
@@ -30,8 +30,14 @@
 //                      the e1's own place; the k-tuples are compacted in order of e1, then sorted by e2, ..., ek in turn;
 //                      the carry is two tables, the open partials and (path 8's rows, through build_carry) the events
 //                      they hold, each once: the link pass flags them, mpatk_cand_kernel makes the candidates
+//   fast_absent        path 11: packed as path 8 (no read row: nothing is packed, the carried partials may still fall due);
+//                      no partial scans: the first cancelling row after every sorted position comes from one count scan
+//                      over chunks (absent_next), then one lane per partial decides cancelled / due at p / open
+//                      (absent_state_kernel); outputs compacted in arrival order, keyed sorted by (p, creation ordinal of
+//                      the instance) and projected here, since their timestamp and trigger are no event's
 #include <string>
 
+#include "absent_dev.h"
 #include "fastpath.h"
 #include "mpat_dev.h"
 #include "mpatk_dev.h"
@@ -147,6 +153,10 @@ constexpr Labels kMPatLabels = {"mpat_facts", "mpat_pack", "mpat_sort",  nullptr
 constexpr Labels kMPatKLabels = {"mpatk_facts", "mpatk_pack", "mpatk_sort",  "mpatk_cand",
                                  "mpatk_count", "mpatk_scan", "mpatk_emit",  "mpatk_carry",
                                  "k-state pattern closed form over several streams"};
+
+constexpr Labels kAbsLabels = {"absent_facts", "absent_pack", "absent_sort",  nullptr,
+                               "absent_count", "absent_scan", "absent_emit",  "absent_carry",
+                               "timeout closed form"};
 
 // ---- begin / leave. own_marks: the driver's marks are the batch's only ones (same-stream); otherwise the entry
 // point's own marks come first, and the first label here times from the last of them
@@ -982,6 +992,261 @@ int64_t fast_pat_k(const FastArgs& a, const int32_t* sid, const MPatKPlan& p, in
   carry.pn = pk;
   carry.pw = pw;
   return carry_out(b, a, o, ncand, nattr, h.ts_last, carry, fs, 10, L, m, false, sid);
+}
+
+namespace {
+__global__ void absent_set_creation_kernel(int64_t* __restrict__ ks, int64_t state_slots, int word,
+                                           const int64_t* __restrict__ create, int64_t n) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < n) ks[(int64_t)word * state_slots + k] = create[k];
+}
+}  // namespace
+
+void absent_set_creation(int64_t* ks, int64_t state_slots, int word, const int64_t* create, int64_t n, hipStream_t s) {
+  if (n <= 0) return;
+  if (n > state_slots) throw std::runtime_error("timeout closed form: more instances than state slots");
+  hipLaunchKernelGGL(absent_set_creation_kernel, seq_grid(n, 256), dim3(256), 0, s, ks, state_slots, word, create, n);
+}
+
+void AbsentInst::reserve(int64_t rows_needed) {
+  if (rows_needed <= cap) return;
+  int64_t* p = nullptr;
+  const int64_t c = std::max<int64_t>(rows_needed, std::max<int64_t>(cap * 2, 1024));
+  SM_HIP(hipMalloc(&p, (size_t)c * 16));
+  if (rows) SM_HIP(hipFree(rows));
+  rows = p;
+  cap = c;
+}
+
+void AbsentInst::release() {
+  if (rows) (void)hipFree(rows);
+  rows = nullptr;
+  n = cap = 0;
+}
+
+int64_t fast_absent(const FastArgs& a, const int32_t* sid, const int64_t* clk, const AbsentPlan& p, int nattr,
+                    const char* blob_dev, FastState& fs, FastCarry& carry, AbsentInst& inst,
+                    const std::function<AbsentOut(int64_t)>& out, Scratch& sc, hipStream_t s, FastTimings* tm) {
+  const Labels& L = kAbsLabels;
+  const int64_t n = a.n;
+  if (n == 0) return 0;
+  const int64_t nc = carry.n;
+  if (n >= 0x7fffffffll || n + nc >= 0x7fffffffll || p.wait < 1) return FAST_OUTSIDE;
+  if (p.stream[0] < 0 || p.stream[0] >= kMSeqStreams || p.stream[1] < 0 || p.stream[1] >= kMSeqStreams)
+    return FAST_OUTSIDE;
+  const bool keyed = p.keyed;
+  Batch b(sc, s, tm, false);
+  const int cw = 3 + nattr;
+  const int64_t ntiles = (n + kSeqTile - 1) / kSeqTile;
+
+  MSeqSrc src = mseq_src(n, sid, p);
+  src.ts = a.ts;
+  src.ordinals = a.ordinals;
+  src.obase = a.ordinal_base;
+
+  // ---- facts: a read row below the clock (read back with the facts), then path 8's
+  uint32_t* below = (uint32_t*)sc.take(4);
+  SM_HIP(hipMemsetAsync(below, 0, 4, s));
+  hipLaunchKernelGGL(absent_clock_kernel, dim3((unsigned)std::min<int64_t>(ntiles, 2048)), dim3(kSeqBlock), 0, s, sid,
+                     src.read, a.ts, clk, n, below);
+  uint32_t hbelow = 0;
+  SM_HIP(hipMemcpyAsync(&hbelow, below, 4, hipMemcpyDeviceToHost, s));
+  uint32_t* tile_n;
+  const Facts h = mseq_facts(b, a, src, keyed, ntiles, carry, L.facts, &tile_n);
+  if (hbelow) return b.leave(FAST_NON_MONOTONE);
+  const int64_t np = h.np;
+  int kbits;
+  if (const int64_t r = envelope(h, false, keyed, true, carry, cw, p.remap_span, &kbits)) return b.leave(r);
+  const bool wide = kbits > 32;
+
+  const int64_t cand_cap = np + nc;  // every partial at most once
+  const int64_t total = nc + n;      // entries of res
+  const int64_t rtiles = (total + kSeqTile - 1) / kSeqTile;
+  const size_t hist = (size_t)8 << 20;
+  // chunks of the count scan: persistent workgroups, eight per compute unit
+  int cus = fs.cus;
+  if (cus <= 0) {
+    int dev = 0;
+    SM_HIP(hipGetDevice(&dev));
+    SM_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  }
+  const int64_t want = std::max<int64_t>(1, (int64_t)cus * 8);
+  const int64_t per = std::max<int64_t>(kSeqBlock, ((np + want - 1) / want + kSeqBlock - 1) / kSeqBlock * kSeqBlock);
+  const int nchunks = (int)((np + per - 1) / per);
+  const uint64_t runs = keyed ? (kbits >= 62 ? (uint64_t)np : std::min<uint64_t>((uint64_t)np, (1ull << kbits))) : 0;
+  {  // scratch up to the counts, for the worst case, before anything changes. Per read row: sort pairs twice over (+ a
+     // histogram word per 4 rows) and a stream byte, a flag and a cancelling position; per row a count; per entry of
+     // res 4 bytes; per key run a new instance
+    const size_t link = (size_t)np * ((keyed ? (wide ? 27 : 19) : 6) + 5) + (size_t)n * 4 + (size_t)total * 4 +
+                        (size_t)runs * 16 + (size_t)(ntiles + rtiles + nchunks + 8) * 8 + hist;
+    if (sc.used + (size_t)cand_cap * 32 + link + 8192 > sc.cap) return b.leave(FAST_OUTSIDE);
+  }
+  const Out o = take_out(sc, std::max<int64_t>(cand_cap, 1));
+
+  Rows rows;
+  if (np > 0) rows = mseq_pack_sort(b, src, tile_n, ntiles, np, keyed, h.kmin, kbits, L);
+  b.event(1);
+
+  SM_HIP(hipMemsetAsync(o.ctl, 0, 8, s));
+  AbsArgs aa{};
+  aa.np = np;
+  aa.n = n;
+  aa.ts = a.ts;
+  aa.clk = clk;
+  aa.st = a.st;
+  aa.code = a.code;
+  aa.consts = a.consts;
+  aa.c1_off = p.off[0];
+  aa.c1_len = p.len[0];
+  aa.c2_off = p.off[1];
+  aa.c2_len = p.len[1];
+  aa.wait = p.wait;
+  aa.ordinals = a.ordinals;
+  aa.obase = a.ordinal_base;
+  aa.perm = rows.perm;
+  aa.skey = rows.skey;
+  aa.kmin = h.kmin;
+  aa.kmax = h.kmax;
+  aa.sstr = rows.sstr;
+  aa.sid = sid;
+  aa.sa = p.stream[0];
+  aa.sb = p.stream[1];
+  aa.ka = keyed ? p.kcol[p.stream[0]] : nullptr;
+  aa.ka_wide = (int)((p.wide >> p.stream[0]) & 1ull);
+  aa.carry = (const int64_t*)carry.rows;
+  aa.nc = nc;
+  aa.cw = cw;
+  aa.per = per;
+  aa.nchunks = nchunks;
+  aa.res = (int32_t*)sc.take((size_t)total * 4);
+  aa.cand = o.cand;
+  aa.cand_n = o.ctl;
+  const dim3 block(kSeqBlock);
+  // ---- next: the first cancelling row after every sorted position
+  if (np > 0) {
+    aa.fl = (uint8_t*)sc.take((size_t)np);
+    aa.ccnt = (uint32_t*)sc.take((size_t)(nchunks + 1) * 4);
+    aa.rk = (uint32_t*)sc.take((size_t)n * 4);
+    aa.F = (uint32_t*)sc.take((size_t)np * 4);
+    hipLaunchKernelGGL(absent_flag_kernel, dim3((unsigned)nchunks), block, 0, s, aa);
+    hipLaunchKernelGGL(absent_chunk_kernel, dim3(1), block, 0, s, aa.ccnt, nchunks);
+    hipLaunchKernelGGL(absent_next_kernel, dim3((unsigned)nchunks), block, 0, s, aa);
+    b.mark("absent_next");
+  }
+  // ---- state: cancelled, due at p, or open
+  if (wide) hipLaunchKernelGGL(absent_state_kernel<uint64_t>, dim3((unsigned)rtiles), block, 0, s, aa);
+  else hipLaunchKernelGGL(absent_state_kernel<uint32_t>, dim3((unsigned)rtiles), block, 0, s, aa);
+  b.mark("absent_state");
+  b.event(2);
+
+  // ---- the counts: outputs, carry-out candidates, new instances
+  uint32_t* counts = (uint32_t*)sc.take((size_t)(rtiles + 1) * 4);
+  hipLaunchKernelGGL(seq_count_kernel, dim3((unsigned)rtiles), block, 0, s, (const int32_t*)aa.res, total, counts);
+  b.mark(L.count);
+  exclusive_scan_u32(counts, (size_t)rtiles, sc, s, o.ctl + 1);
+  b.mark(L.scan);
+  int64_t* fresh = nullptr;
+  uint32_t hfresh = 0;
+  if (keyed && np > 0) {
+    fresh = (int64_t*)sc.take((size_t)runs * 16);
+    uint32_t* nfresh = (uint32_t*)sc.take(4);
+    SM_HIP(hipMemsetAsync(nfresh, 0, 4, s));
+    const dim3 g = seq_grid(np, kSeqBlock);
+    if (wide)
+      hipLaunchKernelGGL(absent_inst_kernel<uint64_t>, g, block, 0, s, aa, (const int64_t*)inst.rows, inst.n, fresh, nfresh);
+    else
+      hipLaunchKernelGGL(absent_inst_kernel<uint32_t>, g, block, 0, s, aa, (const int64_t*)inst.rows, inst.n, fresh, nfresh);
+    SM_HIP(hipMemcpyAsync(&hfresh, nfresh, 4, hipMemcpyDeviceToHost, s));
+  }
+  int64_t ncand;
+  const int64_t m = read_counts(b, o, total, L, &ncand);
+  if ((uint64_t)hfresh > runs) {
+    b.leave(0);
+    throw std::runtime_error(std::string(L.what) + ": more new instances than key runs");
+  }
+  const int64_t ni = inst.n + (int64_t)hfresh;
+  // room for the instance table's sort, the outputs' sorts and the carry build, now that the counts are known: still
+  // nothing is changed
+  if (sc.used + (hfresh ? (size_t)ni * 56 + hist : 0) + (size_t)m * (keyed ? 60 : 8) + 2 * hist + 8192 > sc.cap ||
+      o.keep + (size_t)ncand * (size_t)(8 * cw + 44) + hist + 4096 > sc.cap)
+    return b.leave(FAST_OUTSIDE);
+  const AbsentOut ob = out(m);
+
+  // ---- the instances this batch created join the table, which is sorted by key again
+  if (hfresh > 0) {
+    int64_t* all = (int64_t*)sc.take((size_t)ni * 16);
+    int64_t* sorted = (int64_t*)sc.take((size_t)ni * 16);
+    uint64_t* tk = (uint64_t*)sc.take((size_t)ni * 8);
+    uint64_t* tk2 = (uint64_t*)sc.take((size_t)ni * 8);
+    uint32_t* ti = (uint32_t*)sc.take((size_t)ni * 4);
+    uint32_t* ti2 = (uint32_t*)sc.take((size_t)ni * 4);
+    if (inst.n > 0) SM_HIP(hipMemcpyAsync(all, inst.rows, (size_t)inst.n * 16, hipMemcpyDeviceToDevice, s));
+    SM_HIP(hipMemcpyAsync(all + 2 * inst.n, fresh, (size_t)hfresh * 16, hipMemcpyDeviceToDevice, s));
+    const dim3 g = seq_grid(ni, kSeqBlock);
+    hipLaunchKernelGGL(absent_inst_keys_kernel, g, block, 0, s, (const int64_t*)all, ni, tk, ti);
+    const bool alt = radix_sort_pairs<uint64_t>(tk, tk2, ti, ti2, (size_t)ni, 0, 64, sc, s);
+    hipLaunchKernelGGL(absent_inst_gather_kernel, g, block, 0, s, (const int64_t*)all, (const uint32_t*)(alt ? ti2 : ti), ni,
+                       sorted);
+    if (ni > inst.cap) {
+      SM_HIP(hipStreamSynchronize(s));  // the kernels above read the old rows
+      inst.reserve(ni);
+    }
+    SM_HIP(hipMemcpyAsync(inst.rows, sorted, (size_t)ni * 16, hipMemcpyDeviceToDevice, s));
+    inst.n = ni;
+    b.mark("absent_inst");
+  }
+
+  // ---- the outputs in order of res (carried rows in carry order, then row order): unkeyed that is the order of p;
+  // keyed, stable sorts by the instance's creation ordinal, then by p
+  if (m > 0) {
+    uint32_t* pv = (uint32_t*)sc.take((size_t)m * 4);
+    uint32_t* xv = (uint32_t*)sc.take((size_t)m * 4);
+    hipLaunchKernelGGL(absent_emit_kernel, dim3((unsigned)rtiles), block, 0, s, (const int32_t*)aa.res, total,
+                       (const uint32_t*)counts, pv, xv);
+    b.mark(L.emit);
+    AbsProj pa{};
+    pa.pv = pv;
+    pa.xv = xv;
+    if (keyed) {
+      int64_t* cr = (int64_t*)sc.take((size_t)m * 8);
+      uint64_t* ck = (uint64_t*)sc.take((size_t)m * 8);
+      uint64_t* ck2 = (uint64_t*)sc.take((size_t)m * 8);
+      uint32_t* idx = (uint32_t*)sc.take((size_t)m * 4);
+      uint32_t* idx2 = (uint32_t*)sc.take((size_t)m * 4);
+      uint32_t* pk = (uint32_t*)sc.take((size_t)m * 4);
+      uint32_t* pk2 = (uint32_t*)sc.take((size_t)m * 4);
+      const dim3 g = seq_grid(m, kSeqBlock);
+      hipLaunchKernelGGL(absent_create_kernel, g, block, 0, s, aa, (const uint32_t*)xv, m, (const int64_t*)inst.rows, inst.n,
+                         cr, ck, idx);
+      // creation ordinals are ordinals of rows up to this batch's last
+      const int64_t omax = a.ordinal_base + (np > 0 ? h.omax : 0);
+      const int cbits = omax < 0 ? 64 : std::min(64, std::max(1, bits_of((uint64_t)omax)));
+      if (radix_sort_pairs<uint64_t>(ck, ck2, idx, idx2, (size_t)m, 0, cbits, sc, s)) std::swap(idx, idx2);
+      hipLaunchKernelGGL(absent_pkeys_kernel, g, block, 0, s, (const uint32_t*)pv, (const uint32_t*)idx, m, pk);
+      if (sort_pairs(false, pk, pk2, idx, idx2, m, std::max(1, bits_of((uint64_t)n)), b)) std::swap(idx, idx2);
+      pa.order = idx;
+      pa.cr = cr;
+      b.mark("absent_order");
+    }
+    pa.m = m;
+    pa.nc = nc;
+    pa.carry = (const int64_t*)carry.rows;
+    pa.cw = cw;
+    pa.st = a.st;
+    pa.ts = a.ts;
+    pa.ordinals = a.ordinals;
+    pa.obase = a.ordinal_base;
+    pa.wait = p.wait;
+    pa.blob = blob_dev;
+    pa.e1 = ob.e1;
+    pa.vals = ob.vals;
+    pa.ts_out = ob.ts;
+    pa.pos = ob.pos;
+    pa.create = ob.create;
+    hipLaunchKernelGGL(absent_project_kernel, seq_grid(m, kSeqBlock), block, 0, s, pa);
+    b.mark("absent_project");
+  }
+  return carry_out(b, a, o, ncand, nattr, np > 0 ? h.ts_last : carry.ts_last, carry, fs, 11, L, m);
 }
 
 }  // namespace sm

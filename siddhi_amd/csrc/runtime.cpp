@@ -359,6 +359,8 @@ struct QueryRt {
   int64_t n_out = 0;         // output records read back since the counter was last taken
   FastState fast;            // v2 kernels' persistent look-back state
   FastCarry carry;           // open partials carried across device batches (closed-form queries)
+  AbsentInst abs_inst;       // the timeout closed form (path 11): the partition instances and their creation ordinals
+  DBuf abs_out;              // its outputs' trigger positions and creation ordinals (device)
   // dense partition-key ids for the closed form (remap_keys): 0 = not decided yet, 1 = keys become dense ids (the
   // carry holds ids), 2 = the raw key column is used
   int remap = 0;
@@ -367,7 +369,8 @@ struct QueryRt {
   bool nfa_mode = false;     // a closed-form query handed to the NFA kernel for good (nfa_device_batch)
   int level = 0;             // chaining depth: 0 reads input streams only, L reads a stream a level L-1 query fills
   int nfa_kernel_used = 0;   // 1 = query-specialised NFA kernel, 2 = interpreter (last batch this query ran on the NFA)
-  // last device batch: 9 = pattern over two streams, 8 = adjacent runs over several streams, 7 = adjacent runs (k-state
+  // last device batch: 11 = timeout `every A -> not B for W`, 10 = k-state pattern over several streams,
+  // 9 = pattern over two streams, 8 = adjacent runs over several streams, 7 = adjacent runs (k-state
   // sequence), 6 = adjacent pairs (sequence), 5 = NFA kernel, 3 = bucket stack, 2 = onesweep form, 1 = general form
   int fast_path_used = 0;
   // what sm_app_device_project needs of the last closed-form batch: its stream, event times, ordinals, and the
@@ -398,6 +401,7 @@ struct QueryRt {
   int64_t pool_compactions = 0;
   ~QueryRt() {
     carry.release();
+    abs_inst.release();
     dense.release();
   }
 };
@@ -1252,6 +1256,8 @@ void read_outputs(sm_app* a, int qidx, const void* dev, int64_t n, std::vector<H
     } else if (cq.fast_every_within || cq.fast_seq_adjacent || cq.fast_pat_ms) {  // two hidden refs: (e1, e2)
       h.e1 = rf[cq.hdr.nrefs_vis];
       h.e2 = rf[cq.hdr.nrefs_vis + 1];
+    } else if (cq.fast_absent) {  // one hidden ref: e1
+      h.e1 = h.e2 = rf[cq.hdr.nrefs_vis];
     }
     h.qidx = qidx;
     outs.push_back(h);
@@ -1369,7 +1375,7 @@ void compact_pool(sm_app* a, QueryRt& q, int64_t nkeys, hipStream_t hs) {
 // One pattern / sequence query over a batch: select its streams' records, group them by partition key, run the
 // NFA kernel (one lane per key) and read its output records back for ordered delivery.
 void run_pattern_query(sm_app* a, int qi, const EvArrays& ev, int64_t N, std::vector<HostOut>& outs, hipStream_t hs,
-                       FastTimings* tm = nullptr) {
+                       FastTimings* tm = nullptr, bool create_all = false) {
   QueryRt& q = *a->queries[qi];
   const DQuery& h = q.cq.hdr;
   size_t stride = sizeof(OutRec) + h.nsel * sizeof(DVal) + h.nrefs * sizeof(int64_t);
@@ -1436,7 +1442,7 @@ void run_pattern_query(sm_app* a, int qi, const EvArrays& ev, int64_t N, std::ve
   b.key_pos = key_pos;
   b.lane_compact = lane_compact_ok(b, N, h.node_words, (int)a->ast.streams.size(), a->sc, hs, &b.lane_ord_base) ? 1 : 0;
   b.lane_ev = (const int64_t*)a->sc.take((size_t)std::max<int64_t>(nq, 1) * LaneEv::words(h.node_words, b.lane_compact) * 8);
-  b.create_all = !partitioned;
+  b.create_all = !partitioned || create_all;  // (create_all: every slot of the key table becomes a lane now)
   b.out = q.out.p;
   b.out_count = (uint32_t*)a->d_count.p;
   b.out_cap = (uint32_t)cap;
@@ -1543,9 +1549,16 @@ size_t batch_scratch(const sm_app* a, int64_t N) {
 // refs), and the outputs' Event data in nfa_proj for sm_app_device_project.
 void nfa_outs_to_device(sm_app* a, QueryRt& q, std::vector<HostOut>& outs, int64_t nc, int64_t ordinal_base,
                         hipStream_t hs) {
-  std::stable_sort(outs.begin(), outs.end(), [](const HostOut& x, const HostOut& y) {
-    return x.r.pos != y.r.pos ? x.r.pos < y.r.pos : x.r.seq < y.r.seq;
-  });
+  if (q.cq.fast_absent)  // timer records of several instances share a position: the delivery order (out_before)
+    std::stable_sort(outs.begin(), outs.end(), [](const HostOut& x, const HostOut& y) {
+      if (out_before(x.r, y.r)) return true;
+      if (out_before(y.r, x.r)) return false;
+      return x.r.seq < y.r.seq;
+    });
+  else
+    std::stable_sort(outs.begin(), outs.end(), [](const HostOut& x, const HostOut& y) {
+      return x.r.pos != y.r.pos ? x.r.pos < y.r.pos : x.r.seq < y.r.seq;
+    });
   const size_t ar = (size_t)q.cq.match_arity();  // 2, or k words per tuple for a k-state sequence
   std::vector<uint32_t> pairs(outs.size() * ar);
   for (size_t k = 0; k < outs.size(); ++k) {
@@ -1553,6 +1566,8 @@ void nfa_outs_to_device(sm_app* a, QueryRt& q, std::vector<HostOut>& outs, int64
       throw std::runtime_error("query '" + q.cq.name + "': internal error in the hand-over of carried partials");
     if (ar > 2) {
       for (size_t m = 0; m < ar; ++m) pairs[ar * k + m] = (uint32_t)(outs[k].tuple[m] - ordinal_base);
+    } else if (ar == 1) {  // the timeout: e1 alone
+      pairs[k] = (uint32_t)(outs[k].e1 - ordinal_base);
     } else {
       pairs[2 * k] = (uint32_t)(outs[k].e1 - ordinal_base);
       pairs[2 * k + 1] = (uint32_t)(outs[k].e2 - ordinal_base);
@@ -1699,33 +1714,70 @@ int64_t nfa_device_batch(sm_app* a, int qi, int s, size_t n, const int64_t* d_ts
 void mseq_replay_carry(sm_app* a, int qi, hipStream_t hs) {
   QueryRt& q = *a->queries[qi];
   const int64_t nc = q.nfa_mode ? 0 : q.carry.n;
+  // the timeout (fast_absent, path 11) also hands over its partition instances: the outputs of instances that fall due
+  // at one position come in the order the instances were created, so the key table gets them in that order and, once
+  // the replay has made every one of them a lane (a heartbeat row stands in when no row is carried), each lane's
+  // creation ordinal is set to the instance's. Keys that were given dense ids go back to their values
+  std::vector<int64_t> inst_create;
+  if (q.cq.fast_absent && !q.nfa_mode && q.cq.partition >= 0 && q.abs_inst.n > 0 && q.keys.nslots == 0) {
+    const int64_t ni = q.abs_inst.n;
+    std::vector<int64_t> rows((size_t)ni * 2);
+    SM_HIP(hipMemcpy(rows.data(), q.abs_inst.rows, rows.size() * 8, hipMemcpyDeviceToHost));
+    if (q.remap == 1) {
+      std::vector<int64_t> dk((size_t)q.dense.nslots);
+      if (!dk.empty()) SM_HIP(hipMemcpy(dk.data(), q.dense.slot_keys, dk.size() * 8, hipMemcpyDeviceToHost));
+      for (int64_t i = 0; i < ni; ++i) {
+        if (rows[2 * i] < 0 || rows[2 * i] >= (int64_t)dk.size())
+          throw std::runtime_error("query '" + q.cq.name + "': an instance without a key id");
+        rows[2 * i] = dk[(size_t)rows[2 * i]];
+      }
+    }
+    std::vector<int64_t> order((size_t)ni);
+    for (int64_t i = 0; i < ni; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](int64_t x, int64_t y) { return rows[2 * x + 1] < rows[2 * y + 1]; });
+    std::vector<int64_t> keys((size_t)ni);
+    inst_create.resize((size_t)ni);
+    for (int64_t i = 0; i < ni; ++i) {
+      keys[i] = rows[2 * order[i]];
+      inst_create[i] = rows[2 * order[i] + 1];
+    }
+    q.keys.load(keys.data(), (int32_t)ni, hs);
+  }
+  q.abs_inst.n = 0;
+  const bool lanes = !inst_create.empty();
   q.nfa_mode = true;
-  if (nc == 0) {
+  if (nc == 0 && !lanes) {
     q.carry.reset();
     return;
   }
+  const int64_t nr = std::max<int64_t>(nc, 1);  // rows of the replay batch
   const int s0 = q.cq.streams.at(0);
   const auto& attrs = a->streams[s0].def->attrs;
   const int nattr = (int)attrs.size();
   if (nattr > kMaxAttrs) throw std::runtime_error("stream has more attributes than the device path supports");
   // the pattern over two streams (fast_pat_ms, path 9) carries open partials: e1 rows, all on e1's stream and without the
   // stream word. Replayed in (key, ordinal) order they re-create their partials and emit nothing: no e2 is among them
-  const bool pat = q.cq.fast_pat_ms;
-  if (q.carry.width != (pat ? 3 : 4) + nattr)
+  // So does the timeout (fast_absent, path 11): the replayed e1 rows re-open their partials and schedule their timers at
+  // ts + W, which lies above the clock (an open partial is not due yet), so they emit nothing; in `A -> not A` a carried
+  // later row is no cancelling one, or the earlier partials of its key would not be in the carry. Its instance table
+  // is dropped: the NFA creates an instance again at its first event
+  const bool pat = q.cq.fast_pat_ms || q.cq.fast_absent;
+  const int pat_stream = q.cq.fast_absent ? q.cq.fast_abs_stream[0] : q.cq.fast_pat_stream[0];
+  if (nc > 0 && q.carry.width != (pat ? 3 : 4) + nattr)
     throw std::runtime_error("query '" + q.cq.name + "': carried rows of another form");
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   size_t off = 0;
   std::vector<size_t> col_off(nattr);
   for (int k = 0; k < nattr; ++k) {
     col_off[k] = off;
-    off += al((size_t)nc * width_of((int)attrs[k].type));
+    off += al((size_t)nr * width_of((int)attrs[k].type));
   }
   const size_t ts_off = off;
-  off += al((size_t)nc * 8);
+  off += al((size_t)nr * 8);
   const size_t ord_off = off;
-  off += al((size_t)nc * 8);
+  off += al((size_t)nr * 8);
   const size_t sid_off = off;
-  off += al((size_t)nc * 4);
+  off += al((size_t)nr * 4);
   a->d_rp.ensure(off);
   char* base = (char*)a->d_rp.p;
   CarryCols cc{};
@@ -1738,8 +1790,14 @@ void mseq_replay_carry(sm_app* a, int qi, hipStream_t hs) {
   cc.ts = (int64_t*)(base + ts_off);
   cc.ord = (int64_t*)(base + ord_off);
   cc.sid = pat ? nullptr : (int32_t*)(base + sid_off);
-  if (pat) SM_HIP(hipMemsetD32Async((hipDeviceptr_t)(base + sid_off), q.cq.fast_pat_stream[0], (size_t)nc, hs));
-  carry_rows_to_columns((const int64_t*)q.carry.rows, nc, cc, hs);
+  if (nc == 0) {  // no carried row: one heartbeat row at the clock, which no query reads
+    SM_HIP(hipMemsetAsync(base, 0, off, hs));
+    SM_HIP(hipMemsetD32Async((hipDeviceptr_t)(base + sid_off), -1, 1, hs));
+    SM_HIP(hipMemcpyAsync(base + ts_off, &a->clock, 8, hipMemcpyHostToDevice, hs));
+  } else {
+    if (pat) SM_HIP(hipMemsetD32Async((hipDeviceptr_t)(base + sid_off), pat_stream, (size_t)nc, hs));
+    carry_rows_to_columns((const int64_t*)q.carry.rows, nc, cc, hs);
+  }
   q.carry.reset();  // handed over below; a failure from here on marks the app failed
   std::vector<NfaStream> nst(a->streams.size());
   memset(nst.data(), 0, nst.size() * sizeof(NfaStream));
@@ -1754,15 +1812,15 @@ void mseq_replay_carry(sm_app* a, int qi, hipStream_t hs) {
   SM_HIP(hipMemcpyAsync(a->d_rp_streams.p, nst.data(), nst.size() * sizeof(NfaStream), hipMemcpyHostToDevice, hs));
   for (DBuf* d : {&a->d_ev_row, &a->d_ev_clock, &a->d_ev_ord, &a->d_adv_pos, &a->d_adv_clock, &a->d_adv_wall,
                   &a->d_adv_upto})
-    d->ensure((size_t)nc * 8);
+    d->ensure((size_t)nr * 8);
   a->d_err.ensure(16);
   a->d_count.ensure(16);
-  ensure_scratch(a, batch_scratch(a, nc));
+  ensure_scratch(a, batch_scratch(a, nr));
   a->sc.used = 0;
   const int32_t* sid = (const int32_t*)(base + sid_off);
   const int64_t* ts = (const int64_t*)(base + ts_off);
   int64_t clock_out = a->clock;
-  const int64_t nadv = build_event_index(nc, sid, (int32_t)a->streams.size(), ts, (const int64_t*)(base + ord_off), 0,
+  const int64_t nadv = build_event_index(nr, sid, (int32_t)a->streams.size(), ts, (const int64_t*)(base + ord_off), 0,
                                          a->ast.playback, a->clock, nullptr /* rows = positions */, (int64_t*)a->d_ev_ord.p,
                                          (int64_t*)a->d_ev_clock.p, (int64_t*)a->d_adv_pos.p,
                                          (int64_t*)a->d_adv_clock.p, (int64_t*)a->d_adv_wall.p,
@@ -1774,9 +1832,18 @@ void mseq_replay_carry(sm_app* a, int qi, hipStream_t hs) {
   std::vector<HostOut> outs;
   a->sc.used = 0;
   const int64_t before = q.n_out;
-  run_pattern_query(a, qi, ev, nc, outs, hs);
+  run_pattern_query(a, qi, ev, nr, outs, hs, nullptr, lanes);
   if (q.n_out != before)
     throw std::runtime_error("query '" + q.cq.name + "': internal error in the hand-over of carried rows");
+  if (lanes) {
+    const int64_t ni = (int64_t)inst_create.size();
+    if (q.keys.nslots != ni || q.state_slots < ni)
+      throw std::runtime_error("query '" + q.cq.name + "': internal error in the hand-over of the instances");
+    q.abs_out.ensure((size_t)ni * 8);
+    SM_HIP(hipMemcpyAsync(q.abs_out.p, inst_create.data(), (size_t)ni * 8, hipMemcpyHostToDevice, hs));
+    absent_set_creation((int64_t*)q.ks.p, q.state_slots, q.cq.hdr.ks_misc, (const int64_t*)q.abs_out.p, ni, hs);
+    SM_HIP(hipStreamSynchronize(hs));
+  }
 }
 
 // Whether anything takes query q's outputs: the collect dump, a StreamCallback on its output stream, or a
@@ -2885,6 +2952,134 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
   return m;
 }
 
+// The timeout closed form over one interleaved device batch (CompiledQuery::fast_absent, seqpath.hip fast_absent,
+// path 11). Unlike paths 8-10 it reads and advances the playback clock: the event index of the batch gives the clock at
+// every row (an output's trigger is the first row whose clock reaches its deadline, a heartbeat or a row of an unread
+// stream included), and a->clock becomes the batch's last. The driver projects the outputs itself (their timestamp is
+// no event's): e1's relative ordinals go to dev_pairs, values and timestamps to nfa_proj in the layout
+// sm_app_device_project copies from, and, when something consumes them, HostOut records as the NFA kernel's timer
+// records are: trigger = batch position, phase 0, the instance's creation ordinal, so deliver() makes one chunk per
+// trigger position and instance. Returns the number of outputs, or FAST_OUTSIDE / FAST_NON_MONOTONE with nothing
+// changed.
+int64_t absent_device_events(sm_app* a, int qi, size_t n, const int32_t* d_stream_idx, const int64_t* d_ts,
+                             const void* const* d_cols, const int64_t* d_ordinals, int64_t ordinal_base,
+                             const std::vector<NfaStream>& nst, hipStream_t hs, std::vector<HostOut>& outs) {
+  QueryRt& q = *a->queries[qi];
+  const CompiledQuery& cq = q.cq;
+  const int s0 = cq.fast_abs_stream[0];
+  const NfaStream& d = nst[s0];
+  const char* blob = (const char*)q.blob.p;
+  const int64_t N = (int64_t)n;
+  for (DBuf* b : {&a->d_ev_row, &a->d_ev_clock, &a->d_ev_ord, &a->d_adv_pos, &a->d_adv_clock, &a->d_adv_wall,
+                  &a->d_adv_upto})
+    b->ensure((size_t)std::max<int64_t>(N, 1) * 8);
+  a->sc.used = 0;
+  int64_t clock_out = a->clock;
+  build_event_index(N, d_stream_idx, (int32_t)a->streams.size(), d_ts, d_ordinals, ordinal_base, a->ast.playback, a->clock,
+                    nullptr, d_ordinals ? nullptr : (int64_t*)a->d_ev_ord.p, (int64_t*)a->d_ev_clock.p,
+                    (int64_t*)a->d_adv_pos.p, (int64_t*)a->d_adv_clock.p, (int64_t*)a->d_adv_wall.p,
+                    (int64_t*)a->d_adv_upto.p, &clock_out, a->sc, hs);
+  FastTimings* tm = a->fast_timing ? &a->fast_tm : nullptr;
+  if (tm) tm->mark("event_index", hs);
+  a->sc.used = 0;
+  FastArgs fa{};
+  fa.n = N;
+  fa.ts = d_ts;
+  fa.st = (const NfaStream*)a->d_streams.p + s0;
+  fa.code = (const Instr*)(blob + cq.hdr.off_code);
+  fa.consts = (const DVal*)(blob + cq.hdr.off_const);
+  fa.within = -1;
+  fa.ordinals = d_ordinals;
+  fa.ordinal_base = ordinal_base;
+  AbsentPlan ap;
+  for (int m = 0; m < 2; ++m) {
+    ap.stream[m] = cq.fast_abs_stream[m];
+    ap.off[m] = cq.fast_abs_off[m];
+    ap.len[m] = cq.fast_abs_len[m];
+  }
+  ap.wait = cq.fast_abs_wait;
+  ap.keyed = cq.partition >= 0;
+  for (int m = 0; m < 2; ++m) {  // every read stream's own key attribute
+    const int s = ap.stream[m];
+    ap.read |= 1ull << s;
+    if (!ap.keyed) continue;
+    const int c = cq.fast_abs_keycol.at(s);
+    ap.kcol[s] = d_cols[c];
+    if (d.types[c] == T_LONG) ap.wide |= 1ull << s;
+  }
+  auto dense_keys = [&] {  // the keys as dense ids (remap_keys), one int32 per row, read instead of the columns
+    int64_t* kv = (int64_t*)a->sc.take(n * 8);
+    int32_t* dk = (int32_t*)a->sc.take(n * 4);
+    mseq_gather_keys(N, d_stream_idx, ap, kv, hs);
+    remap_keys(q.dense, kv, T_LONG, N, dk, hs);
+    for (int m = 0; m < 2; ++m) ap.kcol[ap.stream[m]] = dk;
+    ap.wide = 0;
+  };
+  const size_t ns = (size_t)cq.hdr.nsel;
+  auto room = [&](int64_t m) {
+    const size_t mm = (size_t)std::max<int64_t>(m, 1);
+    q.dev_pairs.ensure(std::max<size_t>(mm * 4, 16));
+    q.nfa_proj.ensure(mm * (ns * sizeof(DVal) + 8));
+    q.abs_out.ensure(mm * 16);
+    AbsentOut o{};
+    o.e1 = (uint32_t*)q.dev_pairs.p;
+    o.vals = (DVal*)q.nfa_proj.p;
+    o.ts = (int64_t*)((char*)q.nfa_proj.p + (size_t)m * ns * sizeof(DVal));
+    o.pos = (int64_t*)q.abs_out.p;
+    o.create = (int64_t*)q.abs_out.p + m;
+    return o;
+  };
+  auto closed = [&] {
+    return fast_absent(fa, d_stream_idx, (const int64_t*)a->d_ev_clock.p, ap, d.nattr, blob, q.fast, q.carry, q.abs_inst,
+                       room, a->sc, hs, tm);
+  };
+  const int64_t m = closed_form_batch(a, q, ap.keyed && n > 0, &ap.remap_span, hs, dense_keys, closed);
+  if (m < 0) return m == FAST_NON_MONOTONE ? m : (int64_t)FAST_OUTSIDE;
+  a->clock = clock_out;
+  a->clock_batch_in = a->clock;
+  q.fast_path_used = 11;
+  q.fast.last_path = 11;
+  q.proj_nfa = true;  // sm_app_device_project copies the values and timestamps the driver projected
+  q.proj_ok = false;
+  q.dev_n = m;
+  q.n_out += m;
+  if (m == 0 || !outputs_consumed(a, q)) return m;
+  // the outputs as timer records, in the driver's order = the reference's
+  const int nr = cq.hdr.nrefs_vis;
+  const size_t M = (size_t)m;
+  uint32_t* he1 = (uint32_t*)a->out_arena.take(M * 4);
+  DVal* hv = (DVal*)a->out_arena.take(std::max<size_t>(M * ns, 1) * sizeof(DVal));
+  int64_t* hts = (int64_t*)a->out_arena.take(M * 8);
+  int64_t* hpc = (int64_t*)a->out_arena.take(M * 16);
+  int64_t* hrf = (int64_t*)a->out_arena.take(std::max<size_t>(M * nr, 1) * 8);
+  SM_HIP(hipMemcpyAsync(he1, q.dev_pairs.p, M * 4, hipMemcpyDeviceToHost, hs));
+  if (ns) SM_HIP(hipMemcpyAsync(hv, q.nfa_proj.p, M * ns * sizeof(DVal), hipMemcpyDeviceToHost, hs));
+  SM_HIP(hipMemcpyAsync(hts, (char*)q.nfa_proj.p + M * ns * sizeof(DVal), M * 8, hipMemcpyDeviceToHost, hs));
+  SM_HIP(hipMemcpyAsync(hpc, q.abs_out.p, M * 16, hipMemcpyDeviceToHost, hs));
+  SM_HIP(hipStreamSynchronize(hs));
+  const size_t base = outs.size();
+  outs.resize(base + M);
+  for (size_t k = 0; k < M; ++k) {
+    const int64_t e1 = ordinal_base + (int32_t)he1[k];
+    for (int r = 0; r < nr; ++r) hrf[k * nr + r] = e1;  // every visible reference reads e1
+    HostOut& h = outs[base + k];
+    memset(&h.r, 0, sizeof(h.r));
+    h.r.pos = hpc[k];
+    h.r.create = hpc[M + k];
+    h.r.ts = hts[k];
+    h.r.phase = 0;
+    h.r.query = cq.hdr.query_order;
+    h.r.seq = (int32_t)k;
+    h.vals = hv + k * ns;
+    h.nvals = (int)ns;
+    h.refs = hrf + k * nr;
+    h.nrefs = nr;
+    h.qidx = qi;
+    h.e1 = h.e2 = e1;
+  }
+  return m;
+}
+
 // Outputs of device-batch queries to their consumers (deliver() hands them out even when only the collect dump
 // takes them).
 void deliver_device(sm_app* a, std::vector<HostOut>& douts, std::vector<DevOut>& draw) {
@@ -3139,7 +3334,9 @@ void flush(sm_app* a) {
     // (paths 8 and 9)
     for (size_t qi = 0; qi < a->queries.size(); ++qi) {
       QueryRt& q = *a->queries[qi];
-      if (!(q.cq.fast_seq_ms || q.cq.fast_pat_ms || q.cq.fast_pat_k) || q.nfa_mode || q.nfa_used || !q.carry.active) continue;
+      if (!(q.cq.fast_seq_ms || q.cq.fast_pat_ms || q.cq.fast_pat_k || q.cq.fast_absent) || q.nfa_mode || q.nfa_used ||
+          !q.carry.active)
+        continue;
       bool staged = false;
       for (int s : q.cq.streams) staged |= a->streams[s].rows > 0;
       if (staged) mseq_replay_carry(a, (int)qi, a->stream);
@@ -3588,6 +3785,7 @@ int sm_app_set_option(sm_app* a, const char* key, int64_t value) {
         q->pool_used = 0;
         q->dev_n = 0;
         q->carry.reset();
+        q->abs_inst.n = 0;
         q->dense.clear(a->stream);
         q->remap = 0;
       }
@@ -3711,8 +3909,10 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
     QueryRt* msq = nullptr;
     // Likewise the pattern `every e1=A -> e2=B within T` over two streams (CompiledQuery::fast_pat_ms, path 9).
     // And its k-state sibling (CompiledQuery::fast_pat_k, path 10).
+    // And the timeout `every e1=A -> not B for W` (CompiledQuery::fast_absent, path 11).
     if (a->queries.size() == 1 &&
-        (a->queries[0]->cq.fast_seq_ms > 0 || a->queries[0]->cq.fast_pat_ms || a->queries[0]->cq.fast_pat_k > 0) &&
+        (a->queries[0]->cq.fast_seq_ms > 0 || a->queries[0]->cq.fast_pat_ms || a->queries[0]->cq.fast_pat_k > 0 ||
+         a->queries[0]->cq.fast_absent) &&
         a->streams.size() <= 64)
       msq = a->queries[0].get();
     size_t need = batch_scratch(a, N);
@@ -3723,6 +3923,10 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
       // the pattern: a result word and two sort pairs per carried row too; its carry build is sized by the candidates
       // the batch leaves (fast_pat_ms checks that before anything changes)
       if (msq->cq.fast_pat_ms) need += nc * 24;
+      // the timeout: a result word per carried row, a flag, a count and a cancelling position per row, the event
+      // index; its sorts and its carry build are sized by the outputs and candidates the batch leaves (fast_absent
+      // checks that before anything changes)
+      if (msq->cq.fast_absent) need += nc * 8 + n * 16 + (size_t)msq->abs_inst.n * 64;
       // the k-state pattern: result, kept and k - 1 members per row and carried partial, a flag per event, k words and
       // two sort pairs per tuple, the new partials (fast_pat_k checks the last two once they are counted)
       if (const size_t k = (size_t)msq->cq.fast_pat_k) {
@@ -3751,6 +3955,7 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
         const CompiledQuery& cq = q.cq;
         if (ms_tuples && !q.nfa_mode && !q.nfa_used &&
             (pat ? run_progs_ok(cq, cq.fast_pat_off, cq.fast_pat_len, 2)
+                 : cq.fast_absent ? run_progs_ok(cq, cq.fast_abs_off, cq.fast_abs_len, 2)
                  : cq.fast_pat_k ? run_progs_ok(cq, cq.fast_patk_off, cq.fast_patk_len, cq.fast_pat_k)
                                  : run_progs_ok(cq, cq.fast_ms_off, cq.fast_ms_len, cq.fast_seq_ms))) {
           std::vector<HostOut> douts;
@@ -3758,12 +3963,22 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
           a->out_arena.clear();
           q.n_out = 0;
           q.ev_out_n = 0;
-          const int64_t m = interleaved_device_events(a, 0, n, d_stream_idx, d_ts, d_cols, d_ordinals, ordinal_base, nst,
-                                                      hs, draw);
-          if (m >= 0) {  // the closed form leaves the playback clock alone, as on the device-batch path
-            if (!d_ordinals) a->next_ordinal = std::max<int64_t>(a->next_ordinal, ordinal_base + N);
-            deliver_device(a, douts, draw);
-            return;
+          if (cq.fast_absent) {  // this path advances the playback clock itself
+            const int64_t m = absent_device_events(a, 0, n, d_stream_idx, d_ts, d_cols, d_ordinals, ordinal_base, nst, hs,
+                                                   douts);
+            if (m >= 0) {
+              if (!d_ordinals) a->next_ordinal = std::max<int64_t>(a->next_ordinal, ordinal_base + N);
+              deliver_device(a, douts, draw);
+              return;
+            }
+          } else {
+            const int64_t m = interleaved_device_events(a, 0, n, d_stream_idx, d_ts, d_cols, d_ordinals, ordinal_base, nst,
+                                                        hs, draw);
+            if (m >= 0) {  // the closed form leaves the playback clock alone, as on the device-batch path
+              if (!d_ordinals) a->next_ordinal = std::max<int64_t>(a->next_ordinal, ordinal_base + N);
+              deliver_device(a, douts, draw);
+              return;
+            }
           }
         }
         // outside the envelope, event time not monotone under a `within`, or matching state already on the NFA: the
@@ -3908,6 +4123,14 @@ int sm_app_snapshot(sm_app* a, uint8_t* buf, size_t cap, size_t* len) {
         SM_HIP(hipMemcpy(rows.data(), q.carry.rows, rows.size() * 8, hipMemcpyDeviceToHost));
         w.raw(rows.data(), rows.size() * 8);
       }
+      if (q.cq.fast_absent) {  // the timeout's instances and their creation ordinals
+        w.put<int64_t>(q.abs_inst.n);
+        if (q.abs_inst.n > 0) {
+          std::vector<int64_t> rows((size_t)q.abs_inst.n * 2);
+          SM_HIP(hipMemcpy(rows.data(), q.abs_inst.rows, rows.size() * 8, hipMemcpyDeviceToHost));
+          w.raw(rows.data(), rows.size() * 8);
+        }
+      }
       if (q.cq.fast_pat_k) {  // the open partials of the k-state pattern (the rows above: the events they hold)
         w.put<int64_t>(q.carry.pn);
         w.put<int32_t>(q.carry.pw);
@@ -4037,6 +4260,21 @@ int sm_app_restore(sm_app* a, const uint8_t* buf, size_t len) {
         q.carry.n = cn;
       }
       q.carry.width = cw;
+      q.abs_inst.n = 0;
+      if (q.cq.fast_absent) {
+        const int64_t ni = r.get<int64_t>();
+        if (ni < 0 || ni > INT32_MAX) throw std::runtime_error("CannotRestoreSiddhiAppStateException: bad instance table");
+        if (ni > 0) {
+          std::vector<int64_t> rows((size_t)ni * 2);
+          r.raw(rows.data(), rows.size() * 8);
+          for (int64_t i = 1; i < ni; ++i)  // sorted by key, each key once: the kernels search it
+            if (rows[2 * i] <= rows[2 * (i - 1)])
+              throw std::runtime_error("CannotRestoreSiddhiAppStateException: bad instance table");
+          q.abs_inst.reserve(ni);
+          SM_HIP(hipMemcpy(q.abs_inst.rows, rows.data(), rows.size() * 8, hipMemcpyHostToDevice));
+          q.abs_inst.n = ni;
+        }
+      }
       if (q.cq.fast_pat_k) {
         const int64_t pn = r.get<int64_t>();
         const int32_t pw = r.get<int32_t>();

@@ -22,6 +22,9 @@ fast_timing. Each step starts from a fresh runtime state (option reset), as benc
     python tools/seq_bench.py --query pattern_chain ...     # the three-state pattern `every e1=A[c1] -> e2=B[c2] within T
                                                         # -> e3=A[c3] within T` on the same two-way stream index:
                                                         # fast_path 10 (kernels/mpatk_dev.h); routes as for --query streams
+    python tools/seq_bench.py --query absent ...            # the timeout `every e1=A[c1] -> not B[c2] for 1 sec` on the same
+                                                        # two-way stream index, @app:playback: fast_path 11
+                                                        # (kernels/absent_dev.h); routes as for --query streams
 
 Step time is a host clock around work that ends in a device synchronise; a run without a GPU fails."""
 import argparse
@@ -52,17 +55,19 @@ QUERY_ABA = ("@info(name='q') from every e1=A[price>20], e2=B[price>e1.price], e
 QUERY_PAT_ABA = ("@info(name='q') from every e1=A[price>20] -> e2=B[price>e1.price] within 1 sec -> "
                  "e3=A[price>e2.price] within 1 sec "
                  "select e1.timestamp as i, e2.timestamp as j, e3.timestamp as l insert into OutputStream;")
+QUERY_ABSENT = ("@info(name='q') from every e1=A[price>20] -> not B[price>70] for 1 sec "
+                "select e1.timestamp as i insert into OutputStream;")
 
 
-STREAM_QUERIES = ("streams", "streams3", "pattern_streams", "pattern_chain")
+STREAM_QUERIES = ("streams", "streams3", "pattern_streams", "pattern_chain", "absent")
 
 
 def apps(query):
     if query in STREAM_QUERIES:
         q = {"streams": QUERY_AB, "streams3": QUERY_ABA, "pattern_streams": QUERY_PAT_AB,
-             "pattern_chain": QUERY_PAT_ABA}[query]
-        return {"keyed": SCHEMA_AB + "partition with (symbol of A, symbol of B) begin " + q + " end;",
-                "unkeyed": SCHEMA_AB + q}
+             "pattern_chain": QUERY_PAT_ABA, "absent": QUERY_ABSENT}[query]
+        head = ("@app:playback " if query == "absent" else "") + SCHEMA_AB  # timers run on the events' clock
+        return {"keyed": head + "partition with (symbol of A, symbol of B) begin " + q + " end;", "unkeyed": head + q}
     q = QUERY3 if query == "three" else QUERY
     return {"keyed": SCHEMA + "partition with (symbol of StockStream) begin " + q + " end;", "unkeyed": SCHEMA + q}
 
@@ -76,6 +81,8 @@ LABELS += ["mpat_facts", "mpat_pack", "mpat_sort", "mpat_link", "mpat_count", "m
            "mpat_carry"]
 LABELS += ["mpatk_facts", "mpatk_pack", "mpatk_sort", "mpatk_link", "mpatk_count", "mpatk_scan", "mpatk_cand", "mpatk_emit",
            "mpatk_order", "mpatk_parts", "mpatk_carry"]
+LABELS += ["absent_facts", "absent_pack", "absent_sort", "absent_next", "absent_state", "absent_count", "absent_scan",
+           "absent_inst", "absent_emit", "absent_order", "absent_project", "absent_carry"]
 
 
 def precompile(query):
@@ -112,7 +119,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--route", choices=["closed", "nfa"], default="closed")
     ap.add_argument("--forms", default="keyed,unkeyed")
-    ap.add_argument("--query", choices=["pair", "three", "streams", "streams3", "pattern_streams", "pattern_chain"], default="pair")
+    ap.add_argument("--query", choices=["pair", "three", "streams", "streams3", "pattern_streams", "pattern_chain", "absent"],
+                    default="pair")
     ap.add_argument("--precompile", action="store_true")
     ap.add_argument("--precompile-one")
     a = ap.parse_args()
