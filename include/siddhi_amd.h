@@ -230,6 +230,14 @@ int sm_app_process_device_batch(sm_app* app, const char* stream_id, size_t n, co
  * reaches that time, unless a B event of its partition instance passing c2 arrives before. Unlike the other closed
  * forms it advances the playback clock. It carries the e1 events still waiting and hands over to the NFA kernel as the
  * pattern does, also when a row of a read stream lies below the clock.
+ * The logical absent `every e1=A[c1] -> not B[c2] and e3=C[c3] within T` of an @app:playback app (either operand order;
+ * streams of one schema, B not C, c2 reading the B event and constants only, c3 and the select reading e1 and e3, no
+ * having; partitioned: each read stream keyed by one INT / LONG attribute of its own) runs a closed form too under the
+ * same conditions ("fast_path:<query>" = 12, "match_arity:<query>" = 2: (e1, e3) pairs as the pattern's): every A event
+ * passing c1 takes the first later C event of its partition instance that passes c3, and the pair comes out iff that
+ * event lies inside T and no B event of the instance passing c2 came in between. It carries the e1 events still open,
+ * advances the playback clock and hands over to the NFA kernel as the pattern does. Without a `within` the query runs
+ * on the NFA kernel.
  * "output_events:<query>" (sm_app_get_stat) = output events of the last such batch; "nfa_kernel:<query>" = which NFA
  * kernel ran it (1 = query-specialised, 2 = interpreter, 0 = none yet). */
 int sm_app_process_device_events(sm_app* app, size_t n, const int32_t* d_stream_idx, const int64_t* d_timestamps,

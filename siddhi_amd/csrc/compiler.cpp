@@ -975,6 +975,69 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
         }
       }
     }
+    // ---- the logical absent: every e1=A[c1] -> not B[c2] and e3=C[c3] within T, in either operand order, over streams
+    // of one schema, B not C (kernels/mpat_nand_dev.h). The within on the logical element is part of the form: it bounds
+    // the open partials and every scan. c2 reads the B event and constants only, so one cancelling row cancels every
+    // pending partial of its key; c3 reads e1 and e3; no program reads a timestamp or a stream-context column
+    if (q.input == InputKind::PATTERN && root_el->kind == StateKind::NEXT && !root_el->has_within && !q.having &&
+        root_el->a->kind == StateKind::EVERY && root_el->a->a->kind == StateKind::STREAM && !root_el->a->has_within &&
+        !root_el->a->a->has_within && root_el->b->kind == StateKind::LOGICAL && root_el->b->has_within &&
+        root_el->b->ltype == LogicalType::AND && (int)pres.size() == 3 && h.nslots == 3 && app.playback) {
+      const StateElem* lb = root_el->b->a.get();
+      const StateElem* lc = root_el->b->b.get();
+      if (lb->kind != StateKind::ABSENT) std::swap(lb, lc);
+      bool ok = lb->kind == StateKind::ABSENT && lc->kind == StateKind::STREAM && !lb->has_wait && !lb->has_within &&
+                !lc->has_within && lb->stream_id != lc->stream_id && pres[0].kind == PK_STREAM && pres[0].stateId == 0;
+      int pb = -1, pc = -1;
+      for (int m = 1; ok && m < 3; ++m) {
+        if (pres[m].kind == PK_ABSENT_LOGICAL) pb = m;
+        else if (pres[m].kind == PK_LOGICAL) pc = m;
+      }
+      ok = ok && pb > 0 && pc > 0;
+      const int slot_b = ok ? pres[pb].stateId : -1, slot_c = ok ? pres[pc].stateId : -1;
+      for (size_t r = 0; ok && r < refs.size(); r += 2)
+        if (!(refs[r] == 0 || refs[r] == slot_c) || !(refs[r + 1] == 0 || refs[r + 1] == kCurrent)) ok = false;
+      for (int m = 0; ok && m < 3; ++m)
+        for (int i = 0; ok && i < pres[m].progLen; ++i) {
+          const Instr& in = code[pres[m].progOff + i];
+          if (in.op == OP_TS || in.op == OP_COL) ok = false;
+          if (in.op != OP_VAR) continue;
+          if (!(in.b == 0 || in.b == kCurrent)) ok = false;
+          if (m == 0 ? in.a != 0 : m == pb ? in.a != slot_b : !(in.a == 0 || in.a == slot_c)) ok = false;
+        }
+      const int ss[3] = {ok ? lw.metas[0].stream : -1, ok ? stream_index(app, lb->stream_id) : -1,
+                         ok ? stream_index(app, lc->stream_id) : -1};
+      std::vector<int> keycol(app.streams.size(), -1);
+      for (int m = 0; ok && m < 3; ++m) {
+        const StreamDef& d0 = app.streams[ss[0]];
+        const StreamDef& d = app.streams[ss[m]];
+        ok = d.attrs.size() == d0.attrs.size();
+        for (size_t c = 0; ok && c < d.attrs.size(); ++c) ok = d.attrs[c].type == d0.attrs[c].type;
+        if (!ok || partition < 0) continue;
+        // partitioned: every read stream keyed by one INT / LONG attribute of its own
+        ok = false;
+        for (auto& w : app.partitions[partition].with)
+          if (w.stream_id == d.id && w.key->kind == ExprKind::VAR && w.key->stream_ref.empty()) {
+            const int c = d.index_of(w.key->attr);
+            if (c >= 0 && (d.attrs[c].type == AttrType::INT || d.attrs[c].type == AttrType::LONG)) {
+              keycol[ss[m]] = c;
+              ok = true;
+            }
+          }
+      }
+      if (ok) {
+        cq.fast_pat_nand = true;
+        cq.fast_nand_keycol = keycol;
+        cq.fast_nand_within = root_el->b->within_ms;
+        cq.fast_nand_slot3 = slot_c;
+        const int pm[3] = {0, pb, pc};
+        for (int m = 0; m < 3; ++m) {
+          cq.fast_nand_stream[m] = ss[m];
+          cq.fast_nand_off[m] = pres[pm[m]].progOff;
+          cq.fast_nand_len[m] = pres[pm[m]].progLen;
+        }
+      }
+    }
   }
   h.npre = (int)pres.size();
   h.npost = (int)posts.size();
@@ -990,6 +1053,7 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
   for (int m = 0; m < cq.fast_seq_ms; ++m) refs.insert(refs.end(), {m, 0});
   for (int m = 0; m < cq.fast_pat_k; ++m) refs.insert(refs.end(), {m, 0});
   if (cq.fast_absent) refs.insert(refs.end(), {0, 0});  // hidden e1 ordinal, likewise
+  if (cq.fast_pat_nand) refs.insert(refs.end(), {0, 0, cq.fast_nand_slot3, 0});  // hidden (e1, e3) ordinals, likewise
   h.nrefs = (int)refs.size() / 2;
   h.nconst = (int)consts.size();
   // per-key state layout (int64 words)

@@ -96,6 +96,21 @@ struct CompiledQuery {
   int fast_abs_off[2] = {0, 0}, fast_abs_len[2] = {0, 0};
   int64_t fast_abs_wait = 0;
   std::vector<int> fast_abs_keycol;
+  // fast path: every e1=A[c1] -> not B[c2] and e3=C[c3] within T (either operand order) over streams of one schema, B
+  // not C, c2 reading the B event and constants only, c3 reading e1 and e3, the select reading e1 and e3, no having,
+  // @app:playback (pattern: every A event passing c1 waits for the first later C event of its partition instance that
+  // passes c3; the pair is emitted iff that event lies inside T and no B event of the instance passing c2 came in
+  // between; kernels/mpat_nand_dev.h). A mark of its own: such a query runs through the interleaved entry point only.
+  // fast_nand_stream = the app streams of A, B and C; fast_nand_off / len = c1, c2 (over B's slot alone) and c3 (state
+  // context: slot 0 and e3's slot fast_nand_slot3, which is 1 or 2 with the operand order); fast_nand_within = T (always
+  // >= 0); fast_nand_keycol[s] as fast_ms_keycol. The plan carries the hidden (e1, e3) ordinal refs after the visible
+  // ones; match_arity() stays 2.
+  bool fast_pat_nand = false;
+  int fast_nand_stream[3] = {0, 0, 0};
+  int fast_nand_off[3] = {0, 0, 0}, fast_nand_len[3] = {0, 0, 0};
+  int fast_nand_slot3 = 0;
+  int64_t fast_nand_within = -1;
+  std::vector<int> fast_nand_keycol;
   // uint32 words per device match tuple: k, 2 for every other state query, 1 for a filter (its kept row) and for the
   // timeout (its e1)
   int match_arity() const {

@@ -46,7 +46,7 @@ struct FastState {
   int walk_wgs_per_cu = 0;  // resident walk workgroups per CU
   // pipeline of the last batch: 2 = sort / walk, 3 = bucket stack; seqpath.hip: 6 = adjacent pairs, 7 = adjacent runs,
   // 8 = adjacent runs over several streams, 9 = the pattern over two streams, 10 = the k-state pattern over several
-  // streams, 11 = the timeout `every A -> not B for W`
+  // streams, 11 = the timeout `every A -> not B for W`, 12 = the logical absent `every A -> not B and C within T`
   int last_path = 0;
 };
 
@@ -232,6 +232,21 @@ struct AbsentOut {
 int64_t fast_absent(const FastArgs& a, const int32_t* sid, const int64_t* clk, const AbsentPlan& p, int nattr,
                     const char* blob_dev, FastState& fs, FastCarry& carry, AbsentInst& inst,
                     const std::function<AbsentOut(int64_t)>& out, Scratch& sc, hipStream_t s, FastTimings* tm = nullptr);
+
+// The logical absent `every e1=A[c1] -> not B[c2] and e3=C[c3] within T` over up to three streams of one schema on an
+// interleaved batch (seqpath.hip, mpat_nand_dev.h has the rule and the kernels).
+struct PNandPlan : MSeqKeys {
+  int stream[3] = {0, 0, 0};       // app streams of A, B and C (B is not C)
+  int off[3] = {0, 0, 0}, len[3] = {0, 0, 0};  // c1 (over e1), c2 (over the B event alone), c3 (over e1 and e3)
+  int64_t within = -1;             // T >= 0
+};
+
+// a.st, `sid`, key_remap and FAST_KEY_SPAN as fast_seq_ms; (e1, e3) pairs, their order (e3, e1), pairs_cap, the carry (the
+// open partials' e1 rows: no e3 yet, no cancelling row yet, not expired at the batch's last read row) and both error
+// results as fast_pat_ms. Sets fs.last_path = 12.
+int64_t fast_pat_nand(const FastArgs& a, const int32_t* sid, const PNandPlan& p, int nattr, FastState& fs,
+                      FastCarry& carry, uint32_t* pairs_out, int64_t pairs_cap, Scratch& sc, hipStream_t s,
+                      FastTimings* tm = nullptr);
 
 // The hand-over of the instances to the NFA kernel: word `word` of the per-key state of slots 0 .. n - 1 (ks: word-major,
 // one column of state_slots per word) becomes create[slot], the instance's creation ordinal.

@@ -1,5 +1,5 @@
-// Host entries of the six sequence closed forms (fastpath.h has their contracts, seq_dev.h / mseq_dev.h / mpat_dev.h /
-// mpatk_dev.h / absent_dev.h the rules and the kernels). Every driver runs one batch through the same stages, each written once below:
+// Host entries of the seven sequence closed forms (fastpath.h has their contracts, seq_dev.h / mseq_dev.h / mpat_dev.h /
+// mpatk_dev.h / absent_dev.h / mpat_nand_dev.h the rules and the kernels). Every driver runs one batch through the same stages, each written once below:
 //   begin      Batch: the timing start, the scratch mark, and leave(), which every return goes through
 //   facts      one streaming pass over the keys, event times and ordinals, plus the carried ordinals; its read-back is
 //              the only host round trip before anything is changed (Facts: the same fields for SeqFacts and MSeqFacts)
@@ -35,11 +35,14 @@
 //                      over chunks (absent_next), then one lane per partial decides cancelled / due at p / open
 //                      (absent_state_kernel); outputs compacted in arrival order, keyed sorted by (p, creation ordinal of
 //                      the instance) and projected here, since their timestamp and trigger are no event's
+//   fast_pat_nand      path 12: path 9 with path 11's count scan in front of the link pass: pnand_link_kernel ends a
+//                      partial's scan at its next cancelling row as well; everything after the link pass is path 9's
 #include <string>
 
 #include "absent_dev.h"
 #include "fastpath.h"
 #include "mpat_dev.h"
+#include "mpat_nand_dev.h"
 #include "mpatk_dev.h"
 #include "mseq_dev.h"
 #include "seq_dev.h"
@@ -157,6 +160,10 @@ constexpr Labels kMPatKLabels = {"mpatk_facts", "mpatk_pack", "mpatk_sort",  "mp
 constexpr Labels kAbsLabels = {"absent_facts", "absent_pack", "absent_sort",  nullptr,
                                "absent_count", "absent_scan", "absent_emit",  "absent_carry",
                                "timeout closed form"};
+
+constexpr Labels kPNandLabels = {"pnand_facts", "pnand_pack", "pnand_sort",  nullptr,
+                                 "pnand_count", "pnand_scan", "pnand_emit",  "pnand_carry",
+                                 "logical-absent pattern closed form"};
 
 // ---- begin / leave. own_marks: the driver's marks are the batch's only ones (same-stream); otherwise the entry
 // point's own marks come first, and the first label here times from the last of them
@@ -1247,6 +1254,164 @@ int64_t fast_absent(const FastArgs& a, const int32_t* sid, const int64_t* clk, c
     b.mark("absent_project");
   }
   return carry_out(b, a, o, ncand, nattr, np > 0 ? h.ts_last : carry.ts_last, carry, fs, 11, L, m);
+}
+
+int64_t fast_pat_nand(const FastArgs& a, const int32_t* sid, const PNandPlan& p, int nattr, FastState& fs,
+                      FastCarry& carry, uint32_t* pairs_out, int64_t pairs_cap, Scratch& sc, hipStream_t s,
+                      FastTimings* tm) {
+  const Labels& L = kPNandLabels;
+  const int64_t n = a.n;
+  if (n == 0) return 0;
+  const int64_t nc = carry.n;
+  if (n >= 0x7fffffffll || n + nc >= 0x7fffffffll || p.within < 0 || p.stream[1] == p.stream[2]) return FAST_OUTSIDE;
+  for (int m = 0; m < 3; ++m)
+    if (p.stream[m] < 0 || p.stream[m] >= kMSeqStreams) return FAST_OUTSIDE;
+  const bool keyed = p.keyed;
+  Batch b(sc, s, tm, false);
+  const int cw = 3 + nattr;
+  const int64_t ntiles = (n + kSeqTile - 1) / kSeqTile;
+
+  MSeqSrc src = mseq_src(n, sid, p);
+  src.ts = a.ts;
+  src.ordinals = a.ordinals;
+  src.obase = a.ordinal_base;
+
+  uint32_t* tile_n;
+  const Facts h = mseq_facts(b, a, src, keyed, ntiles, carry, L.facts, &tile_n);
+  const int64_t np = h.np;
+  int kbits;
+  if (const int64_t r = envelope(h, true, keyed, np + nc <= pairs_cap, carry, cw, p.remap_span, &kbits))
+    return b.leave(r);
+  if (np == 0) {  // no row of a stream the query reads: its carried rows wait
+    fs.last_path = 12;
+    return b.leave(0);
+  }
+  const bool wide = kbits > 32;
+
+  const int64_t cand_cap = np + nc;
+  const int64_t total = nc + n;  // entries of `res`
+  const int64_t rtiles = (total + kSeqTile - 1) / kSeqTile;
+  const size_t hist = (size_t)8 << 20;
+  // chunks of the count scan: persistent workgroups, eight per compute unit (as path 11)
+  int cus = fs.cus;
+  if (cus <= 0) {
+    int dev = 0;
+    SM_HIP(hipGetDevice(&dev));
+    SM_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  }
+  const int64_t want = std::max<int64_t>(1, (int64_t)cus * 8);
+  const int64_t per = std::max<int64_t>(kSeqBlock, ((np + want - 1) / want + kSeqBlock - 1) / kSeqBlock * kSeqBlock);
+  const int nchunks = (int)((np + per - 1) / per);
+  {  // scratch up to the counts, for the worst case, before anything changes: path 9's, and per read row a flag and a
+     // cancelling position, per row a count, per chunk a count
+    const size_t link = (size_t)np * ((keyed ? (wide ? 43 : 35) : 22) + 5) + (size_t)n * 4 + (size_t)nc * 17 +
+                        (size_t)total * 4 + (size_t)(ntiles + rtiles + nchunks + 8) * 8 + hist;
+    if (sc.used + (size_t)cand_cap * 32 + link + 8192 > sc.cap) return b.leave(FAST_OUTSIDE);
+  }
+  const Out o = take_out(sc, cand_cap);
+
+  const Rows rows = mseq_pack_sort(b, src, tile_n, ntiles, np, keyed, h.kmin, kbits, L);
+  b.event(1);
+
+  // ---- next: the first cancelling row (stream B and c2) after every sorted position
+  const dim3 block(kSeqBlock);
+  AbsArgs aa{};
+  aa.np = np;
+  aa.n = n;
+  aa.ts = a.ts;
+  aa.st = a.st;
+  aa.code = a.code;
+  aa.consts = a.consts;
+  aa.c2_off = p.off[1];
+  aa.c2_len = p.len[1];
+  aa.perm = rows.perm;
+  aa.skey = rows.skey;
+  aa.sstr = rows.sstr;
+  aa.sid = sid;
+  aa.sb = p.stream[1];
+  aa.per = per;
+  aa.nchunks = nchunks;
+  aa.fl = (uint8_t*)sc.take((size_t)np);
+  aa.ccnt = (uint32_t*)sc.take((size_t)(nchunks + 1) * 4);
+  aa.rk = (uint32_t*)sc.take((size_t)n * 4);
+  aa.F = (uint32_t*)sc.take((size_t)np * 4);
+  hipLaunchKernelGGL(absent_flag_kernel, dim3((unsigned)nchunks), block, 0, s, aa);
+  hipLaunchKernelGGL(absent_chunk_kernel, dim3(1), block, 0, s, aa.ccnt, nchunks);
+  hipLaunchKernelGGL(absent_next_kernel, dim3((unsigned)nchunks), block, 0, s, aa);
+  b.mark("pnand_next");
+
+  // ---- link: every partial (carried rows, then A rows passing c1) scans forward in its key run for its e3, up to its
+  // cancel bound
+  SM_HIP(hipMemsetAsync(o.ctl, 0, 8, s));
+  PNandArgs pa{};
+  MPatArgs& ma = pa.m;
+  ma.np = np;
+  ma.n = n;
+  ma.ts = a.ts;
+  ma.st = a.st;
+  ma.code = a.code;
+  ma.consts = a.consts;
+  ma.c1_off = p.off[0];
+  ma.c1_len = p.len[0];
+  ma.c2_off = p.off[2];
+  ma.c2_len = p.len[2];
+  ma.within = p.within;
+  ma.ts_last = h.ts_last;
+  ma.ordinals = a.ordinals;
+  ma.obase = a.ordinal_base;
+  ma.perm = rows.perm;
+  ma.skey = rows.skey;
+  ma.kmin = h.kmin;
+  ma.kmax = h.kmax;
+  ma.sstr = rows.sstr;
+  ma.sid = sid;
+  ma.sa = p.stream[0];
+  ma.sb = p.stream[2];
+  ma.carry = (const int64_t*)carry.rows;
+  ma.nc = nc;
+  ma.cw = cw;
+  ma.res = (int32_t*)sc.take((size_t)total * 4);
+  ma.cand = o.cand;
+  ma.cand_n = o.ctl;
+  pa.fl = aa.fl;
+  pa.rk = aa.rk;
+  pa.F = aa.F;
+  pa.nf = aa.ccnt + nchunks;
+  uint32_t* counts = (uint32_t*)sc.take((size_t)(rtiles + 1) * 4);
+  // rows that are not read have no lane: their entries are "none"
+  if (np < n) SM_HIP(hipMemsetD32Async((hipDeviceptr_t)(ma.res + nc), (int)kSeqNone, (size_t)n, s));
+  const dim3 lgrid((unsigned)((nc + np + kSeqTile - 1) / kSeqTile));
+  if (wide) hipLaunchKernelGGL(pnand_link_kernel<uint64_t>, lgrid, block, 0, s, pa);
+  else hipLaunchKernelGGL(pnand_link_kernel<uint32_t>, lgrid, block, 0, s, pa);
+  b.mark("pnand_link");
+  b.event(2);
+
+  // ---- the two counts: pairs and carry-out candidates
+  hipLaunchKernelGGL(seq_count_kernel, dim3((unsigned)rtiles), block, 0, s, (const int32_t*)ma.res, total, counts);
+  b.mark(L.count);
+  exclusive_scan_u32(counts, (size_t)rtiles, sc, s, o.ctl + 1);
+  b.mark(L.scan);
+  int64_t ncand;
+  const int64_t m = read_counts(b, o, pairs_cap, L, &ncand);
+  // room for the carry build, now that the number of candidates is known: still nothing is changed
+  if (o.keep + (size_t)ncand * (size_t)(8 * cw + 44) + hist + 4096 > sc.cap) return b.leave(FAST_OUTSIDE);
+
+  // ---- pairs in order of e1 (carried rows in carry order, then row order), then the stable sort by e3 alone over the
+  // bits of the largest relative ordinal
+  if (m > 0) {
+    uint32_t* jk = (uint32_t*)sc.take((size_t)m * 4);
+    uint32_t* jk2 = (uint32_t*)sc.take((size_t)m * 4);
+    uint32_t* iv = (uint32_t*)sc.take((size_t)m * 4);
+    uint32_t* iv2 = (uint32_t*)sc.take((size_t)m * 4);
+    hipLaunchKernelGGL(mpat_emit_kernel, dim3((unsigned)rtiles), block, 0, s, (const int32_t*)ma.res, total, nc,
+                       (const uint32_t*)counts, a.ordinals, a.ordinal_base, (const int64_t*)carry.rows, cw, jk, iv);
+    b.mark(L.emit);
+    const bool alt = sort_pairs(false, jk, jk2, iv, iv2, m, std::max(1, bits_of((uint64_t)h.omax)), b);
+    hipLaunchKernelGGL(mpat_pairs_kernel, seq_grid(m, kSeqBlock), block, 0, s, (const uint32_t*)(alt ? jk2 : jk),
+                       (const uint32_t*)(alt ? iv2 : iv), m, pairs_out);
+    b.mark("pnand_order");
+  }
+  return carry_out(b, a, o, ncand, nattr, h.ts_last, carry, fs, 12, L, m);
 }
 
 }  // namespace sm

@@ -94,4 +94,9 @@ int64_t build_event_index(int64_t n, const int32_t* sid, int32_t nstreams, const
                           int64_t* ev_clock, int64_t* adv_pos, int64_t* adv_clock, int64_t* adv_wall,
                           int64_t* adv_upto, int64_t* clock_out, Scratch& sc, hipStream_t s);
 
+// build_event_index's clock_out alone, for a playback app's batch of n > 0 rows: max(clock_in, the largest ts). Two
+// launches and an 8-byte copy on s; *clock_out holds the value once s has been synchronised. The scratch it takes may be
+// reused by work that follows on s.
+void batch_clock_async(int64_t n, const int64_t* ts, int64_t clock_in, int64_t* clock_out, Scratch& sc, hipStream_t s);
+
 }  // namespace sm

@@ -1267,4 +1267,15 @@ int64_t build_event_index(int64_t n, const int32_t* sid, int32_t nstreams, const
   return nadv;
 }
 
+void batch_clock_async(int64_t n, const int64_t* ts, int64_t clock_in, int64_t* clock_out, Scratch& sc, hipStream_t s) {
+  *clock_out = clock_in;
+  if (n <= 0) return;
+  const int64_t ntiles = (n + kIxTile - 1) / kIxTile;
+  int64_t* tile_max = (int64_t*)sc.take(ntiles * 8);
+  int64_t* dclock = (int64_t*)sc.take(8);
+  hipLaunchKernelGGL(ts_tile_max_kernel, dim3((unsigned)ntiles), dim3(kIxThreads), 0, s, ts, n, tile_max);
+  hipLaunchKernelGGL(tile_prefix_max_kernel, dim3(1), dim3(kIxThreads), 0, s, tile_max, ntiles, clock_in, dclock);
+  SM_HIP(hipMemcpyAsync(clock_out, dclock, 8, hipMemcpyDeviceToHost, s));
+}
+
 }  // namespace sm

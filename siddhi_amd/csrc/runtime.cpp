@@ -466,6 +466,22 @@ bool run_progs_ok(const CompiledQuery& cq, const int* off, const int* len, int k
   return true;
 }
 
+// The logical absent (fast_pat_nand): c1 reads slot 0, c2 the B event's slot alone, c3 slot 0 and e3's slot, one event
+// each; the same check otherwise.
+bool nand_progs_ok(const CompiledQuery& cq) {
+  const Instr* code = (const Instr*)(cq.blob.data() + cq.hdr.off_code);
+  for (int m = 0; m < 3; ++m)
+    for (int i = 0; i < cq.fast_nand_len[m]; ++i) {
+      const Instr& in = code[cq.fast_nand_off[m] + i];
+      if (in.op == OP_TS || in.op == OP_COL) return false;
+      if (in.op != OP_VAR) continue;
+      if (!(in.b == 0 || in.b == -1)) return false;
+      const int sb = 3 - cq.fast_nand_slot3;  // slots 1 and 2 are the two operands'
+      if (m == 0 ? in.a != 0 : m == 1 ? in.a != sb : !(in.a == 0 || in.a == cq.fast_nand_slot3)) return false;
+    }
+  return true;
+}
+
 }  // namespace
 }  // namespace sm
 
@@ -1253,7 +1269,7 @@ void read_outputs(sm_app* a, int qidx, const void* dev, int64_t n, std::vector<H
       h.tuple = rf + cq.hdr.nrefs_vis;
       h.e1 = h.tuple[0];
       h.e2 = h.tuple[cq.match_arity() - 1];
-    } else if (cq.fast_every_within || cq.fast_seq_adjacent || cq.fast_pat_ms) {  // two hidden refs: (e1, e2)
+    } else if (cq.fast_every_within || cq.fast_seq_adjacent || cq.fast_pat_ms || cq.fast_pat_nand) {  // two hidden refs: (e1, e2)
       h.e1 = rf[cq.hdr.nrefs_vis];
       h.e2 = rf[cq.hdr.nrefs_vis + 1];
     } else if (cq.fast_absent) {  // one hidden ref: e1
@@ -1761,8 +1777,14 @@ void mseq_replay_carry(sm_app* a, int qi, hipStream_t hs) {
   // ts + W, which lies above the clock (an open partial is not due yet), so they emit nothing; in `A -> not A` a carried
   // later row is no cancelling one, or the earlier partials of its key would not be in the carry. Its instance table
   // is dropped: the NFA creates an instance again at its first event
-  const bool pat = q.cq.fast_pat_ms || q.cq.fast_absent;
-  const int pat_stream = q.cq.fast_absent ? q.cq.fast_abs_stream[0] : q.cq.fast_pat_stream[0];
+  // And the logical absent (fast_pat_nand, path 12): the replayed e1 rows re-open their partials in both lists of the
+  // logical element and emit nothing, since no C row is among them unless A = C, and then a carried later row did not
+  // pass c3 against a carried earlier one of its key, or that one would have matched and left the carry. Likewise
+  // with A = B a carried later row is no cancelling one: had it passed c2, the earlier partials of its key would have
+  // a cancelling row and would not be in the carry
+  const bool pat = q.cq.fast_pat_ms || q.cq.fast_absent || q.cq.fast_pat_nand;
+  const int pat_stream = q.cq.fast_absent ? q.cq.fast_abs_stream[0]
+                         : q.cq.fast_pat_nand ? q.cq.fast_nand_stream[0] : q.cq.fast_pat_stream[0];
   if (nc > 0 && q.carry.width != (pat ? 3 : 4) + nattr)
     throw std::runtime_error("query '" + q.cq.name + "': carried rows of another form");
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -2853,7 +2875,10 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
 // from prev_carry, the carried events), a sequence over
 // several streams of one schema (CompiledQuery::fast_seq_ms, fast_seq_ms, path 8: k-tuples in dev_pairs) or the pattern
 // `every e1=A -> e2=B within T` over two streams (CompiledQuery::fast_pat_ms, fast_pat_ms, path 9: (e1, e2) pairs, an e1
-// carried from an earlier batch projected from prev_carry). `nst` are the host copies of the batch's stream
+// carried from an earlier batch projected from prev_carry) or the logical absent `every e1=A -> not B and e3=C within T`
+// (CompiledQuery::fast_pat_nand, fast_pat_nand, path 12: (e1, e3) pairs as path 9's; its app is @app:playback, and once
+// the batch has succeeded a->clock advances to the largest event time of the feed's rows, as path 11 advances it, so
+// that a later hand-over starts from the right clock). `nst` are the host copies of the batch's stream
 // descriptors, already uploaded to d_streams. Returns the number of matches (the projection state set as in
 // device_batch_stream; the outputs that have consumers appended to draw), or FAST_OUTSIDE / FAST_NON_MONOTONE with
 // nothing changed.
@@ -2863,7 +2888,8 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
   QueryRt& q = *a->queries[qi];
   const CompiledQuery& cq = q.cq;
   const bool pat = cq.fast_pat_ms;
-  const int s0 = pat ? cq.fast_pat_stream[0] : cq.streams.at(0);
+  const bool nand = cq.fast_pat_nand;
+  const int s0 = nand ? cq.fast_nand_stream[0] : pat ? cq.fast_pat_stream[0] : cq.streams.at(0);
   const NfaStream& d = nst[s0];
   const char* blob = (const char*)q.blob.p;
   a->sc.used = 0;
@@ -2879,9 +2905,19 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
   MSeqPlan sp;
   MPatPlan pp;
   MPatKPlan kp;
+  PNandPlan np;
   const int patk = cq.fast_pat_k;
   std::vector<int> read;  // the streams the query reads
-  if (patk) {
+  if (nand) {
+    for (int m = 0; m < 3; ++m) {
+      np.stream[m] = cq.fast_nand_stream[m];
+      np.off[m] = cq.fast_nand_off[m];
+      np.len[m] = cq.fast_nand_len[m];
+    }
+    np.within = cq.fast_nand_within;
+    for (int m = 0; m < 3; ++m)
+      if (std::find(read.begin(), read.end(), np.stream[m]) == read.end()) read.push_back(np.stream[m]);
+  } else if (patk) {
     kp.k = patk;
     for (int m = 0; m < patk; ++m) {
       kp.stream[m] = cq.fast_patk_stream[m];
@@ -2908,12 +2944,12 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
     }
     read = cq.streams;
   }
-  MSeqKeys& keys = patk ? static_cast<MSeqKeys&>(kp) : pat ? static_cast<MSeqKeys&>(pp) : sp;
+  MSeqKeys& keys = nand ? static_cast<MSeqKeys&>(np) : patk ? static_cast<MSeqKeys&>(kp) : pat ? static_cast<MSeqKeys&>(pp) : sp;
   keys.keyed = cq.partition >= 0;
   for (int s : read) {  // every read stream's own key attribute
     keys.read |= 1ull << s;
     if (!keys.keyed) continue;
-    const int c = (patk ? cq.fast_patk_keycol : pat ? cq.fast_pat_keycol : cq.fast_ms_keycol).at(s);
+    const int c = (nand ? cq.fast_nand_keycol : patk ? cq.fast_patk_keycol : pat ? cq.fast_pat_keycol : cq.fast_ms_keycol).at(s);
     keys.kcol[s] = d_cols[c];
     if (d.types[c] == T_LONG) keys.wide |= 1ull << s;
   }
@@ -2927,10 +2963,21 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
   };
   // a sequence: k words per match, at most one match per event; the pattern: (e1, e2) per match, at most one per partial
   // the k-state pattern: k words per match, at most one per partial
-  const int64_t cap = patk ? (int64_t)n + q.carry.pn : pat ? (int64_t)n + q.carry.n : (int64_t)n;
-  q.dev_pairs.ensure(std::max<size_t>(patk ? (size_t)cap * 4 * (size_t)patk : pat ? (size_t)cap * 8 : n * 4 * (size_t)sp.k, 16));
+  const int64_t cap = patk ? (int64_t)n + q.carry.pn : pat || nand ? (int64_t)n + q.carry.n : (int64_t)n;
+  q.dev_pairs.ensure(std::max<size_t>(patk ? (size_t)cap * 4 * (size_t)patk : pat || nand ? (size_t)cap * 8 : n * 4 * (size_t)sp.k, 16));
   FastTimings* tm = a->fast_timing ? &a->fast_tm : nullptr;
+  // the logical absent: build_event_index's clock_out alone, the largest event time of the feed's rows (heartbeats and
+  // unread rows included) or the clock before it. One reduction in front of the driver, in stream order; its value is
+  // on the host once the driver's first read-back has synchronised the stream
+  int64_t nand_clock = a->clock;
+  if (nand && n > 0) {
+    batch_clock_async((int64_t)n, d_ts, a->clock, &nand_clock, a->sc, hs);
+    if (tm) tm->mark("pnand_clock", hs);
+    a->sc.used = 0;  // (the driver's kernels follow the reduction on the stream)
+  }
   auto closed = [&] {
+    if (nand)
+      return fast_pat_nand(fa, d_stream_idx, np, d.nattr, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, cap, a->sc, hs, tm);
     if (patk)
       return fast_pat_k(fa, d_stream_idx, kp, d.nattr, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, cap, a->sc, hs, tm);
     return pat ? fast_pat_ms(fa, d_stream_idx, pp, d.nattr, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, cap, a->sc, hs, tm)
@@ -2938,6 +2985,10 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
   };
   const int64_t m = closed_form_batch(a, q, keys.keyed && n > 0, &keys.remap_span, hs, dense_keys, closed);
   if (m < 0) return m == FAST_NON_MONOTONE ? m : (int64_t)FAST_OUTSIDE;
+  if (nand) {  // an @app:playback app: the clock follows the feed as on path 11, so that a hand-over starts from it
+    a->clock = nand_clock;
+    a->clock_batch_in = a->clock;
+  }
   q.fast_path_used = q.fast.last_path;
   q.proj_nfa = false;
   q.proj_desc = d;
@@ -3334,7 +3385,8 @@ void flush(sm_app* a) {
     // (paths 8 and 9)
     for (size_t qi = 0; qi < a->queries.size(); ++qi) {
       QueryRt& q = *a->queries[qi];
-      if (!(q.cq.fast_seq_ms || q.cq.fast_pat_ms || q.cq.fast_pat_k || q.cq.fast_absent) || q.nfa_mode || q.nfa_used ||
+      if (!(q.cq.fast_seq_ms || q.cq.fast_pat_ms || q.cq.fast_pat_k || q.cq.fast_absent || q.cq.fast_pat_nand) ||
+          q.nfa_mode || q.nfa_used ||
           !q.carry.active)
         continue;
       bool staged = false;
@@ -3910,9 +3962,10 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
     // Likewise the pattern `every e1=A -> e2=B within T` over two streams (CompiledQuery::fast_pat_ms, path 9).
     // And its k-state sibling (CompiledQuery::fast_pat_k, path 10).
     // And the timeout `every e1=A -> not B for W` (CompiledQuery::fast_absent, path 11).
+    // And the logical absent `every e1=A -> not B and e3=C within T` (CompiledQuery::fast_pat_nand, path 12).
     if (a->queries.size() == 1 &&
         (a->queries[0]->cq.fast_seq_ms > 0 || a->queries[0]->cq.fast_pat_ms || a->queries[0]->cq.fast_pat_k > 0 ||
-         a->queries[0]->cq.fast_absent) &&
+         a->queries[0]->cq.fast_absent || a->queries[0]->cq.fast_pat_nand) &&
         a->streams.size() <= 64)
       msq = a->queries[0].get();
     size_t need = batch_scratch(a, N);
@@ -3923,6 +3976,8 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
       // the pattern: a result word and two sort pairs per carried row too; its carry build is sized by the candidates
       // the batch leaves (fast_pat_ms checks that before anything changes)
       if (msq->cq.fast_pat_ms) need += nc * 24;
+      // the logical absent: the same, and a flag, a count and a cancelling position per row, and the event index
+      if (msq->cq.fast_pat_nand) need += nc * 24 + n * 16;
       // the timeout: a result word per carried row, a flag, a count and a cancelling position per row, the event
       // index; its sorts and its carry build are sized by the outputs and candidates the batch leaves (fast_absent
       // checks that before anything changes)
@@ -3955,6 +4010,7 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
         const CompiledQuery& cq = q.cq;
         if (ms_tuples && !q.nfa_mode && !q.nfa_used &&
             (pat ? run_progs_ok(cq, cq.fast_pat_off, cq.fast_pat_len, 2)
+                 : cq.fast_pat_nand ? nand_progs_ok(cq)
                  : cq.fast_absent ? run_progs_ok(cq, cq.fast_abs_off, cq.fast_abs_len, 2)
                  : cq.fast_pat_k ? run_progs_ok(cq, cq.fast_patk_off, cq.fast_patk_len, cq.fast_pat_k)
                                  : run_progs_ok(cq, cq.fast_ms_off, cq.fast_ms_len, cq.fast_seq_ms))) {
@@ -3974,7 +4030,7 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
           } else {
             const int64_t m = interleaved_device_events(a, 0, n, d_stream_idx, d_ts, d_cols, d_ordinals, ordinal_base, nst,
                                                         hs, draw);
-            if (m >= 0) {  // the closed form leaves the playback clock alone, as on the device-batch path
+            if (m >= 0) {  // paths 8-10 leave the playback clock alone, as on the device-batch path; path 12 has set it
               if (!d_ordinals) a->next_ordinal = std::max<int64_t>(a->next_ordinal, ordinal_base + N);
               deliver_device(a, douts, draw);
               return;

@@ -25,6 +25,10 @@ fast_timing. Each step starts from a fresh runtime state (option reset), as benc
     python tools/seq_bench.py --query absent ...            # the timeout `every e1=A[c1] -> not B[c2] for 1 sec` on the same
                                                         # two-way stream index, @app:playback: fast_path 11
                                                         # (kernels/absent_dev.h); routes as for --query streams
+    python tools/seq_bench.py --query absent_and ...        # the logical absent `every e1=A[c1] -> not B[c2] and e3=C[c3]
+                                                        # within 1 sec` on a three-way stream index, @app:playback:
+                                                        # fast_path 12 (kernels/mpat_nand_dev.h); routes as for --query
+                                                        # streams
 
 Step time is a host clock around work that ends in a device synchronise; a run without a GPU fails."""
 import argparse
@@ -59,10 +63,21 @@ QUERY_ABSENT = ("@info(name='q') from every e1=A[price>20] -> not B[price>70] fo
                 "select e1.timestamp as i insert into OutputStream;")
 
 
-STREAM_QUERIES = ("streams", "streams3", "pattern_streams", "pattern_chain", "absent")
+SCHEMA_ABC = SCHEMA_AB + "define stream C " + ATTRS
+QUERY_ABSENT_AND = ("@info(name='q') from every e1=A[price>20] -> not B[price>70] and e3=C[price>e1.price] within 1 sec "
+                    "select e1.timestamp as i, e3.timestamp as j insert into OutputStream;")
 
 
-def apps(query):
+STREAM_QUERIES = ("streams", "streams3", "pattern_streams", "pattern_chain", "absent", "absent_and")
+
+
+def apps(query, cancel_above="70"):
+    """cancel_above: c2's constant of --query absent_and (a large one cancels nothing)."""
+    if query == "absent_and":
+        head = "@app:playback " + SCHEMA_ABC
+        q = QUERY_ABSENT_AND.replace("price>70", "price>" + cancel_above)
+        return {"keyed": head + "partition with (symbol of A, symbol of B, symbol of C) begin " + q + " end;",
+                "unkeyed": head + q}
     if query in STREAM_QUERIES:
         q = {"streams": QUERY_AB, "streams3": QUERY_ABA, "pattern_streams": QUERY_PAT_AB,
              "pattern_chain": QUERY_PAT_ABA, "absent": QUERY_ABSENT}[query]
@@ -83,24 +98,27 @@ LABELS += ["mpatk_facts", "mpatk_pack", "mpatk_sort", "mpatk_link", "mpatk_count
            "mpatk_order", "mpatk_parts", "mpatk_carry"]
 LABELS += ["absent_facts", "absent_pack", "absent_sort", "absent_next", "absent_state", "absent_count", "absent_scan",
            "absent_inst", "absent_emit", "absent_order", "absent_project", "absent_carry"]
+LABELS += ["pnand_facts", "pnand_pack", "pnand_sort", "pnand_next", "pnand_link", "pnand_count", "pnand_scan", "pnand_emit",
+           "pnand_order", "pnand_carry", "pnand_clock"]
 
 
-def precompile(query):
+def precompile(query, cancel_above):
     """The NFA route's query-specialised kernels take minutes through hiprtc: compiled here, on a host without a GPU,
     into siddhi_amd/jit_cache (the compact lane-event form a 4-attribute stream takes), one process per plan."""
     import subprocess
-    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--query", query, "--precompile-one", form],
-                              env=dict(os.environ, SM_NFA_JIT_COMPACT="1")) for form in apps(query)]
+    procs = [subprocess.Popen([sys.executable, os.path.abspath(__file__), "--query", query, "--cancel-above", cancel_above,
+                               "--precompile-one", form],
+                              env=dict(os.environ, SM_NFA_JIT_COMPACT="1")) for form in apps(query, cancel_above)]
     sys.exit(max(p.wait() for p in procs))
 
 
-def precompile_one(form, query):
+def precompile_one(form, query, cancel_above):
     import torch  # noqa: F401  (first, as in every run: the library then compiles with the hiprtc torch bundles)
     from siddhi_amd import _lib
     log = ctypes.create_string_buffer(8192)
     size = ctypes.c_size_t()
     t = time.time()
-    rc = _lib.lib().sm_nfa_jit_compile(apps(query)[form].encode(), 0, log, 8192, ctypes.byref(size))
+    rc = _lib.lib().sm_nfa_jit_compile(apps(query, cancel_above)[form].encode(), 0, log, 8192, ctypes.byref(size))
     print(f"{form}: rc {rc}, {size.value} bytes, {time.time() - t:.0f} s {log.value.decode()[:200]}", flush=True)
     sys.exit(rc)
 
@@ -119,15 +137,21 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--route", choices=["closed", "nfa"], default="closed")
     ap.add_argument("--forms", default="keyed,unkeyed")
-    ap.add_argument("--query", choices=["pair", "three", "streams", "streams3", "pattern_streams", "pattern_chain", "absent"],
+    ap.add_argument("--query", choices=["pair", "three", "streams", "streams3", "pattern_streams", "pattern_chain", "absent",
+                                        "absent_and"],
                     default="pair")
+    ap.add_argument("--cancel-above", default="70",
+                    help="--query absent_and: the constant of c2 `not B[price>X]`; the outputs a large X adds are the "
+                         "partials that the default cancels")
     ap.add_argument("--precompile", action="store_true")
     ap.add_argument("--precompile-one")
     a = ap.parse_args()
+    if a.cancel_above != "70" and a.query != "absent_and":
+        ap.error("--cancel-above belongs to --query absent_and")
     if a.precompile_one:
-        precompile_one(a.precompile_one, a.query)
+        precompile_one(a.precompile_one, a.query, a.cancel_above)
     if a.precompile:
-        precompile(a.query)
+        precompile(a.query, a.cancel_above)
     if a.steps < 10:
         print("note: fewer than 10 timed steps", file=sys.stderr)
 
@@ -146,12 +170,14 @@ def main():
         x = ordinals * (0x9E3779B97F4A7C15 - (1 << 64))  # (wraps: a multiply-xorshift hash, one bit of it)
         x = (x ^ (x >> 29)) * (0xBF58476D1CE4E5B9 - (1 << 64))
         sidx = ((x >> 43) & 1).to(torch.int32)
+        if a.query == "absent_and":  # three ways: two more bits of the hash, folded to 0 .. 2
+            sidx = (((x >> 41) & 0xFFFF) % 3).to(torch.int32)
     hs = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     build_id = _lib.lib().sm_build_id().decode()
     torch.cuda.synchronize()
     for form in a.forms.split(","):
         opts = {"nfa_jit": 1} if a.route == "nfa" else {}
-        app = ProductApp(apps(a.query)[form], **opts)
+        app = ProductApp(apps(a.query, a.cancel_above)[form], **opts)
         app.set_collect(False)
         cols = [sym, price, price, ordinals]  # volume is not read: aliased
 
