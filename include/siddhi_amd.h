@@ -238,6 +238,16 @@ int sm_app_process_device_batch(sm_app* app, const char* stream_id, size_t n, co
  * event lies inside T and no B event of the instance passing c2 came in between. It carries the e1 events still open,
  * advances the playback clock and hands over to the NFA kernel as the pattern does. Without a `within` the query runs
  * on the NFA kernel.
+ * The logical pair `every e1=A[c1] -> e2=B[c2] and e3=C[c3] within T`, and the same with `or` (streams of one schema, B
+ * not C, c2 reading e1 and e2, c3 reading e1 and e3, no having; `and`: A is neither B nor C; partitioned: each read
+ * stream keyed by one INT / LONG attribute of its own; @app:playback is not required), runs a closed form too under the
+ * same conditions ("fast_path:<query>" = 13, "match_arity:<query>" = 3: (e1, e2, e3) triples): every A event passing c1
+ * takes the first later B event of its partition instance passing c2 and the first later C event passing c3,
+ * independently. `and` emits the triple at the later of the two iff it lies inside T of e1; `or` emits at the earlier
+ * one iff it lies inside T of e1, with the other member absent (its attributes are null). The outputs come in order of
+ * that completing event, then e1, and carry its timestamp. It carries the open partials, an `and` partial possibly with
+ * one member bound, with the events they hold, and hands over to the NFA kernel as the k-state pattern does. Without
+ * a `within` the query runs on the NFA kernel.
  * "output_events:<query>" (sm_app_get_stat) = output events of the last such batch; "nfa_kernel:<query>" = which NFA
  * kernel ran it (1 = query-specialised, 2 = interpreter, 0 = none yet). */
 int sm_app_process_device_events(sm_app* app, size_t n, const int32_t* d_stream_idx, const int64_t* d_timestamps,
@@ -319,7 +329,10 @@ int sm_order_outputs(const void* d_recs, size_t n, size_t stride, void* d_out, v
 /* Match tuples of the last device batch for a query: n pairs (e1, e2) of ordinals relative to the batch's
  * ordinal_base, uint32[2*n] in device memory, in reference output order (e2 ordinal, then e1 ordinal). A k-state
  * sequence (3 <= k <= 8) has k words per tuple, (e1, ..., ek), uint32[k*n], in order of ek: the words per tuple are
- * the stat "match_arity:<query>". Members carried from an earlier batch are negative as int32. */
+ * the stat "match_arity:<query>". Members carried from an earlier batch are negative as int32. The logical pair
+ * ("fast_path" 13) has three words per tuple, (e1, e2, e3) in the order of the query text, in order of the later of e2 /
+ * e3; a member that `or` left unbound is the word 0x80000000, which no carried member is (a carried member's ordinal lies
+ * less than 2^31 below the batch's base). */
 int sm_app_device_matches(sm_app* app, const char* query_name, const uint32_t** d_pairs, size_t* n);
 /* The same tuples (match_arity uint32 words each; a filter query's kept rows: one) copied into a caller-owned device
  * buffer of cap_bytes on hip_stream (asynchronous); *n = tuples. Lets a caller hand them to its own collectives. */
@@ -338,8 +351,9 @@ typedef struct sm_dval {
 /* QuerySelector.processNoGroupBy (query/selector/QuerySelector.java:124-167) on the device for the outputs of the
  * last device batch of a query: output k (the k-th tuple of sm_app_device_matches, or a filter query's k-th kept
  * row) gets its select list in d_values[k * nsel .. k * nsel + nsel) and its timestamp (the last event's time,
- * StateEvent.timestamp) in d_ts[k] (d_ts may be NULL). An e1 carried from an earlier batch is read from the carried
- * partial; a batch the NFA kernel took returns the values the kernel evaluated. With d_values == NULL only *n and
+ * StateEvent.timestamp) in d_ts[k] (d_ts may be NULL; the logical pair: the time of the later of e2 / e3, and the
+ * attributes of a member `or` left unbound come out with is_null = 1). An e1 carried from an earlier batch is read from
+ * the carried partial; a batch the NFA kernel took returns the values the kernel evaluated. With d_values == NULL only *n and
  * *nsel are set. The batch's columns, event times and ordinals are read again: call it before freeing them.
  * SM_E_UNSUPPORTED when the query's last outputs came from host-API events (they reach the callbacks). */
 int sm_app_device_project(sm_app* app, const char* query_name, sm_dval* d_values, size_t cap_values, int64_t* d_ts,
@@ -352,10 +366,13 @@ int sm_app_device_project(sm_app* app, const char* query_name, sm_dval* d_values
  * kernel; through sm_app_process_device_events (the label event_index first): sequences over several streams 8 =
  * adjacent-run kernels on the read rows (labels mseq_facts, mseq_pack, mseq_sort, mseq_link, mseq_keep, mseq_count,
  * mseq_scan, mseq_emit, mseq_carry), the pattern over two streams 9 (labels mpat_facts, mpat_pack, mpat_sort, mpat_link,
- * mpat_count, mpat_scan, mpat_emit, mpat_order, mpat_carry), 5 = general NFA kernel;
+ * mpat_count, mpat_scan, mpat_emit, mpat_order, mpat_carry), the k-state pattern 10 (labels mpatk_*), the timeout 11
+ * (labels absent_*), the logical absent 12 (labels pnand_*), the logical pair `and` / `or` 13 (labels plog_facts,
+ * plog_pack, plog_sort, plog_link, plog_count, plog_scan, plog_cand, plog_emit, plog_order, plog_parts, plog_carry),
+ * 5 = general NFA kernel;
  * filter queries 3 = filter interpreter, 4 = typed conjunction. "output_events:<query>" = its output count.
  * "match_arity:<query>" = uint32 words per tuple of sm_app_device_matches: k for a k-state sequence of the adjacent-run
- * form, 2 for every other pattern or sequence, 1 for a filter (its kept row).
+ * form, 3 for the logical pair, 2 for every other pattern or sequence, 1 for a filter (its kept row).
  * "kernel_ms:<label>" / "kernel_calls:<label>" and "fast_ms:group" / "fast_ms:walk" / "fast_ms:order" (per-kernel
  * and phase times in ms; need the "fast_timing" option). "nfa_state:<query>" = 1 once a closed-form query's matching
  * state is held by the general NFA kernel for good: host events it could not take on the closed form (a null value,

@@ -1038,6 +1038,72 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
         }
       }
     }
+    // ---- the logical pair of two present events: every e1=A[c1] -> e2=B[c2] and|or e3=C[c3] within T over streams of
+    // one schema, B not C (kernels/mpat_logic_dev.h). The within on the logical element is part of the form: it bounds
+    // the open partials and every scan. c2 reads e1 and e2, c3 reads e1 and e3: neither operand reads the other, so the
+    // two members are found independently. `and`: A is neither B nor C, since the hand-over replays bound e2 / e3 events
+    // on their own streams, and one that passed c1 on A's stream would open a partial that has completed already.
+    // `or`: A may be B or C; its carry holds e1 rows only, and a carried later row did not pass c2 / c3 against a
+    // carried earlier one of its key, or that one would have matched and left the carry
+    if (q.input == InputKind::PATTERN && root_el->kind == StateKind::NEXT && !root_el->has_within && !q.having &&
+        root_el->a->kind == StateKind::EVERY && root_el->a->a->kind == StateKind::STREAM && !root_el->a->has_within &&
+        !root_el->a->a->has_within && root_el->b->kind == StateKind::LOGICAL && root_el->b->has_within &&
+        root_el->b->within_ms >= 0 && (int)pres.size() == 3 && h.nslots == 3) {
+      const StateElem* lb = root_el->b->a.get();
+      const StateElem* lc = root_el->b->b.get();
+      const bool land = root_el->b->ltype == LogicalType::AND;
+      // pres[1] is the first operand of the text and pres[2] the second; the lowering parses the second operand first,
+      // so their slots are read, not assumed
+      bool ok = lb->kind == StateKind::STREAM && lc->kind == StateKind::STREAM && !lb->has_within && !lc->has_within &&
+                lb->stream_id != lc->stream_id && pres[0].kind == PK_STREAM && pres[0].stateId == 0 &&
+                pres[1].kind == PK_LOGICAL && pres[2].kind == PK_LOGICAL;
+      const int slot2 = ok ? pres[1].stateId : -1, slot3 = ok ? pres[2].stateId : -1;
+      ok = ok && slot2 > 0 && slot3 > 0 && slot2 != slot3 && slot2 + slot3 == 3;
+      for (size_t r = 0; ok && r < refs.size(); r += 2)
+        if (refs[r] < 0 || refs[r] > 2 || !(refs[r + 1] == 0 || refs[r + 1] == kCurrent)) ok = false;
+      for (int m = 0; ok && m < 3; ++m)
+        for (int i = 0; ok && i < pres[m].progLen; ++i) {
+          const Instr& in = code[pres[m].progOff + i];
+          if (in.op == OP_TS || in.op == OP_COL) ok = false;
+          if (in.op != OP_VAR) continue;
+          if (!(in.b == 0 || in.b == kCurrent)) ok = false;
+          if (!(in.a == 0 || (m > 0 && in.a == pres[m].stateId))) ok = false;
+        }
+      const int ss[3] = {ok ? lw.metas[0].stream : -1, ok ? stream_index(app, lb->stream_id) : -1,
+                         ok ? stream_index(app, lc->stream_id) : -1};
+      if (ok && land && (ss[0] == ss[1] || ss[0] == ss[2])) ok = false;
+      std::vector<int> keycol(app.streams.size(), -1);
+      for (int m = 0; ok && m < 3; ++m) {
+        const StreamDef& d0 = app.streams[ss[0]];
+        const StreamDef& d = app.streams[ss[m]];
+        ok = d.attrs.size() == d0.attrs.size();
+        for (size_t c = 0; ok && c < d.attrs.size(); ++c) ok = d.attrs[c].type == d0.attrs[c].type;
+        if (!ok || partition < 0) continue;
+        // partitioned: every read stream keyed by one INT / LONG attribute of its own
+        ok = false;
+        for (auto& w : app.partitions[partition].with)
+          if (w.stream_id == d.id && w.key->kind == ExprKind::VAR && w.key->stream_ref.empty()) {
+            const int c = d.index_of(w.key->attr);
+            if (c >= 0 && (d.attrs[c].type == AttrType::INT || d.attrs[c].type == AttrType::LONG)) {
+              keycol[ss[m]] = c;
+              ok = true;
+            }
+          }
+      }
+      if (ok) {
+        cq.fast_pat_logic = land ? 1 : 2;
+        cq.fast_logic_keycol = keycol;
+        cq.fast_logic_within = root_el->b->within_ms;
+        cq.fast_logic_slot[0] = 0;
+        cq.fast_logic_slot[1] = slot2;
+        cq.fast_logic_slot[2] = slot3;
+        for (int m = 0; m < 3; ++m) {
+          cq.fast_logic_stream[m] = ss[m];
+          cq.fast_logic_off[m] = pres[m].progOff;
+          cq.fast_logic_len[m] = pres[m].progLen;
+        }
+      }
+    }
   }
   h.npre = (int)pres.size();
   h.npost = (int)posts.size();
@@ -1054,6 +1120,8 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
   for (int m = 0; m < cq.fast_pat_k; ++m) refs.insert(refs.end(), {m, 0});
   if (cq.fast_absent) refs.insert(refs.end(), {0, 0});  // hidden e1 ordinal, likewise
   if (cq.fast_pat_nand) refs.insert(refs.end(), {0, 0, cq.fast_nand_slot3, 0});  // hidden (e1, e3) ordinals, likewise
+  if (cq.fast_pat_logic)  // hidden (e1, e2, e3) ordinals in the order of the query text, likewise
+    refs.insert(refs.end(), {0, 0, cq.fast_logic_slot[1], 0, cq.fast_logic_slot[2], 0});
   h.nrefs = (int)refs.size() / 2;
   h.nconst = (int)consts.size();
   // per-key state layout (int64 words)

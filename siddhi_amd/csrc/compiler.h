@@ -111,12 +111,30 @@ struct CompiledQuery {
   int fast_nand_slot3 = 0;
   int64_t fast_nand_within = -1;
   std::vector<int> fast_nand_keycol;
-  // uint32 words per device match tuple: k, 2 for every other state query, 1 for a filter (its kept row) and for the
-  // timeout (its e1)
+  // fast path: every e1=A[c1] -> e2=B[c2] and e3=C[c3] within T, or the same with `or`, over streams of one schema, B
+  // not C, c2 reading e1 and e2, c3 reading e1 and e3, no having (pattern: every A event passing c1 takes the first later
+  // B event of its partition instance passing c2 and the first later C event passing c3, independently; `and` emits at
+  // the later of the two, `or` at the earlier with the other side null, iff that event lies inside T of e1;
+  // kernels/mpat_logic_dev.h). fast_pat_logic = 1 (and: A is neither B nor C) or 2 (or); a mark of its own: such a query
+  // runs through the interleaved entry point only. Index m = 0, 1, 2 is e1, e2, e3 in the order of the query text:
+  // fast_logic_stream their app streams, fast_logic_off / len their condition programs (state context: slot 0 and the
+  // member's own slot fast_logic_slot[m]; the lowering numbers the second operand's slot first), fast_logic_within = T
+  // (always >= 0), fast_logic_keycol[s] as fast_ms_keycol. The plan carries the hidden (e1, e2, e3) ordinal refs after the
+  // visible ones; a member that `or` left unbound has no ordinal there.
+  int fast_pat_logic = 0;
+  int fast_logic_stream[3] = {0, 0, 0};
+  int fast_logic_off[3] = {0, 0, 0}, fast_logic_len[3] = {0, 0, 0};
+  int fast_logic_slot[3] = {0, 0, 0};
+  int64_t fast_logic_within = -1;
+  std::vector<int> fast_logic_keycol;
+  // uint32 words per device match tuple: k, 3 for the logical pair, 2 for every other state query, 1 for a filter (its
+  // kept row) and for the timeout (its e1)
   int match_arity() const {
     return hdr.kind == 0 || fast_absent ? 1
-           : fast_seq_k ? fast_seq_k : fast_seq_ms ? fast_seq_ms : fast_pat_k ? fast_pat_k : 2;
+           : fast_seq_k ? fast_seq_k : fast_seq_ms ? fast_seq_ms : fast_pat_k ? fast_pat_k : fast_pat_logic ? 3 : 2;
   }
+  // the closed forms that carry an event table and a partial table of k + 1 words per row (FastCarry::parts): k, or 0
+  int carry_parts_k() const { return fast_pat_k ? fast_pat_k : fast_pat_logic ? 3 : 0; }
 };
 
 struct CompiledPartition {

@@ -46,7 +46,8 @@ struct FastState {
   int walk_wgs_per_cu = 0;  // resident walk workgroups per CU
   // pipeline of the last batch: 2 = sort / walk, 3 = bucket stack; seqpath.hip: 6 = adjacent pairs, 7 = adjacent runs,
   // 8 = adjacent runs over several streams, 9 = the pattern over two streams, 10 = the k-state pattern over several
-  // streams, 11 = the timeout `every A -> not B for W`, 12 = the logical absent `every A -> not B and C within T`
+  // streams, 11 = the timeout `every A -> not B for W`, 12 = the logical absent `every A -> not B and C within T`,
+  // 13 = the logical pair `every A -> B and|or C within T`
   int last_path = 0;
 };
 
@@ -78,8 +79,9 @@ struct FastCarry {
   int width = 0;            // 3 + nattr
   bool active = false;      // a device batch has run for this query: ts_last is valid
   int64_t ts_last = 0;      // event time of the last event of the last batch
-  // fast_pat_k only: the open partials [key, bound events s, global ordinals o1 .. os padded to k - 1], every key's in
-  // order of o1; `rows` are then the events they hold, each once, with the stream as the last word
+  // fast_pat_k and fast_pat_logic only: the open partials [key, bound events s, global ordinals o1 .. os padded to
+  // k - 1], every key's in order of o1 (fast_pat_logic: [key, state, o1, o2], fastpath.h fast_pat_logic); `rows` are
+  // then the events they hold, each once, with the stream as the last word
   int64_t* parts = nullptr;  // device, pn rows of pw words
   int64_t pn = 0, pcap = 0;
   int pw = 0;               // k + 1
@@ -248,6 +250,24 @@ int64_t fast_pat_nand(const FastArgs& a, const int32_t* sid, const PNandPlan& p,
                       FastCarry& carry, uint32_t* pairs_out, int64_t pairs_cap, Scratch& sc, hipStream_t s,
                       FastTimings* tm = nullptr);
 
+// The logical pair `every e1=A[c1] -> e2=B[c2] and|or e3=C[c3] within T` over up to three streams of one schema on an
+// interleaved batch (seqpath.hip, mpat_logic_dev.h has the rule and the kernels).
+struct PLogPlan : MSeqKeys {
+  bool land = true;                // and / or
+  int stream[3] = {0, 0, 0};       // app streams of A, B and C (B is not C; and: A is neither)
+  int off[3] = {0, 0, 0}, len[3] = {0, 0, 0};  // c1 (over e1), c2 (over e1 and e2), c3 (over e1 and e3)
+  int64_t within = -1;             // T >= 0, against e1
+};
+
+// a.st, `sid`, key_remap and FAST_KEY_SPAN as fast_seq_ms. Outputs are (e1, e2, e3) triples as fast_pat_k's (members
+// carried from earlier batches negative as int32; a member `or` left unbound is the word 0x80000000, which no carried
+// member is), in order of (completing member, e1), at most n + carry.pn of them (tuples_cap). The carry is fast_pat_k's:
+// the open partials (FastCarry::parts, rows [key, s, o1, o2]: s = 1 e1 alone, 2 with e2, 3 with e3) and the events they
+// hold. Both error results as fast_pat_k. Sets fs.last_path = 13.
+int64_t fast_pat_logic(const FastArgs& a, const int32_t* sid, const PLogPlan& p, int nattr, FastState& fs,
+                       FastCarry& carry, uint32_t* tuples_out, int64_t tuples_cap, Scratch& sc, hipStream_t s,
+                       FastTimings* tm = nullptr);
+
 // The hand-over of the instances to the NFA kernel: word `word` of the per-key state of slots 0 .. n - 1 (ks: word-major,
 // one column of state_slots per word) becomes create[slot], the instance's creation ordinal.
 void absent_set_creation(int64_t* ks, int64_t state_slots, int word, const int64_t* create, int64_t n, hipStream_t s);
@@ -305,7 +325,10 @@ void pair_project(const uint32_t* pairs, int64_t m, const NfaStream* st_dev, con
                   DVal* out, int64_t* ts_out, Scratch& sc, hipStream_t s, bool rows = false,
                   int64_t* words = nullptr, uint8_t* nulls = nullptr,  // words / nulls: compact form (nsel <= 8)
                   const uint32_t* carry_keys = nullptr, const uint32_t* carry_idx = nullptr, bool sync = true,
-                  int arity = 2);  // arity k > 2: `pairs` are k-tuples (the adjacent-run closed form), slot s = word s
+                  int arity = 2,  // arity k > 2: `pairs` are k-tuples (the adjacent-run closed form), slot s = word s
+                  const int* logic_slot = nullptr);  // the logical pair's triples: word w holds slot logic_slot[w], a
+                                                     // word 0x80000000 is an absent member (its attributes are null),
+                                                     // and ts_out is the event time of the later of e2 / e3
 // The carried partials' e1 ordinals sorted for pair_project (carry_keys / carry_idx, nc each, in sc): a caller
 // projecting one batch's outputs in several launches sorts them once (round 5: device_outputs' segments)
 void pair_project_carry_order(const int64_t* prev_carry, int64_t nc, int cw, int64_t base, Scratch& sc, hipStream_t s,

@@ -1282,15 +1282,26 @@ __global__ void pair_project_kernel(const uint32_t* __restrict__ pairs, int64_t 
 }
 
 // The arity-k sibling (the adjacent-run closed form's k-tuples, 3 <= k <= 8): slot s of output t is the event
-// tuples[k t + s]; any member but the last may be a carried row.
+// tuples[k t + s]; any member but the last may be a carried row. kLogic: the logical pair's triples (e1, e2, e3), word w
+// holding slot lslot[w]; a word 0x80000000 is a member `or` left unbound, whose attributes read as null; the timestamp is
+// that of the later of e2 / e3, the completing member (always a batch row).
+template <bool kLogic>
 struct TupleLoader {
   const NfaStream* st;
   int64_t r[8];        // batch rows
   const int64_t* c[8]; // carry rows, or nullptr
   int k;
+  uint32_t absent;     // kLogic: the slots `or` left unbound
   __device__ StackVal var(const Instr& in) const {
     if (in.op == OP_COL) return col_value(st, in.a, r[k - 1]);
     const int s = in.a < 0 ? 0 : in.a >= k ? k - 1 : in.a;
+    if (kLogic && ((absent >> s) & 1u)) {
+      StackVal v;
+      v.i = 0;
+      v.d = 0;
+      v.null = 1;
+      return v;
+    }
     if (c[s]) {
       StackVal v = uncanon((uint64_t)c[s][3 + in.c], in.t0);
       if (in.t0 == T_STRING) v.null = v.i < 0;
@@ -1300,28 +1311,35 @@ struct TupleLoader {
   }
 };
 
+template <bool kLogic>
 __global__ void tuple_project_kernel(const uint32_t* __restrict__ tuples, int64_t m, int arity,
                                      const NfaStream* __restrict__ st, const int64_t* __restrict__ ord, int64_t n,
                                      int64_t base, const int64_t* __restrict__ ts, const int64_t* __restrict__ crow,
                                      int cw, const uint32_t* __restrict__ ckey, const uint32_t* __restrict__ cidx,
                                      int64_t nc, const char* __restrict__ blob, DVal* __restrict__ out,
                                      int64_t* __restrict__ ts_out, int64_t* __restrict__ words,
-                                     uint8_t* __restrict__ nulls) {
+                                     uint8_t* __restrict__ nulls, int lslot1, int lslot2) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= m) return;
   const DQuery* q = (const DQuery*)blob;
   const Instr* code = (const Instr*)(blob + q->off_code);
   const DVal* consts = (const DVal*)(blob + q->off_const);
   const int32_t* sel = (const int32_t*)(blob + q->off_sel);
-  TupleLoader ld;
+  TupleLoader<kLogic> ld;
   ld.st = st;
   ld.k = arity;
+  ld.absent = 0;
   for (int s = 0; s < 8; ++s) {
     ld.r[s] = 0;
     ld.c[s] = nullptr;
-    if (s >= arity) continue;
-    const uint32_t e = tuples[t * arity + s];
-    if ((int32_t)e < 0 && nc > 0) {  // a carried member: its row in the previous carry, by ordinal
+  }
+  for (int w = 0; w < 8; ++w) {
+    if (w >= arity) continue;
+    const int s = !kLogic || w == 0 ? w : w == 1 ? lslot1 : lslot2;
+    const uint32_t e = tuples[t * arity + w];
+    if (kLogic && e == 0x80000000u) {
+      ld.absent |= 1u << s;
+    } else if ((int32_t)e < 0 && nc > 0) {  // a carried member: its row in the previous carry, by ordinal
       const uint32_t want = (uint32_t)((int32_t)e + 0x80000000ll);
       int64_t lo = 0, hi = nc - 1;
       while (lo < hi) {
@@ -1350,6 +1368,11 @@ __global__ void tuple_project_kernel(const uint32_t* __restrict__ tuples, int64_
     }
   }
   if (words) nulls[t] = (uint8_t)nb;
+  if (kLogic) {
+    const int32_t e2 = (int32_t)tuples[t * arity + 1], e3 = (int32_t)tuples[t * arity + 2];
+    if (ts_out) ts_out[t] = ts[batch_row(ord, n, base, (uint32_t)(e2 > e3 ? e2 : e3))];
+    return;
+  }
   if (ts_out) ts_out[t] = ts[ld.r[arity - 1]];  // StateEvent.timestamp: the last event's event time
 }
 }  // namespace
@@ -1372,14 +1395,18 @@ void pair_project_carry_order(const int64_t* prev_carry, int64_t nc, int cw, int
 void pair_project(const uint32_t* pairs, int64_t m, const NfaStream* st_dev, const int64_t* ord, int64_t n,
                   int64_t base, const int64_t* ts, const int64_t* prev_carry, int64_t nc, int cw, const char* blob_dev,
                   DVal* out, int64_t* ts_out, Scratch& sc, hipStream_t s, bool rows, int64_t* words,
-                  uint8_t* nulls, const uint32_t* carry_keys, const uint32_t* carry_idx, bool sync, int arity) {
+                  uint8_t* nulls, const uint32_t* carry_keys, const uint32_t* carry_idx, bool sync, int arity,
+                  const int* logic_slot) {
   if (m <= 0) return;
   const size_t mark = sc.used;
   const uint32_t *ck = carry_keys, *ci = carry_idx;
   if (nc > 0 && !rows && !ck) pair_project_carry_order(prev_carry, nc, cw, base, sc, s, &ck, &ci);
-  if (arity > 2 && !rows)
-    hipLaunchKernelGGL(tuple_project_kernel, grid_of(m), dim3(256), 0, s, pairs, m, arity, st_dev, ord, n, base, ts,
-                       prev_carry, cw, ck, ci, nc, blob_dev, out, ts_out, words, nulls);
+  if (logic_slot && arity == 3 && !rows)
+    hipLaunchKernelGGL(tuple_project_kernel<true>, grid_of(m), dim3(256), 0, s, pairs, m, arity, st_dev, ord, n, base, ts,
+                       prev_carry, cw, ck, ci, nc, blob_dev, out, ts_out, words, nulls, logic_slot[1], logic_slot[2]);
+  else if (arity > 2 && !rows)
+    hipLaunchKernelGGL(tuple_project_kernel<false>, grid_of(m), dim3(256), 0, s, pairs, m, arity, st_dev, ord, n, base, ts,
+                       prev_carry, cw, ck, ci, nc, blob_dev, out, ts_out, words, nulls, 0, 0);
   else
     hipLaunchKernelGGL(pair_project_kernel, grid_of(m), dim3(256), 0, s, pairs, m, st_dev, ord, n, base, ts, prev_carry,
                        cw, ck, ci, nc, blob_dev, rows, out, ts_out, words, nulls);

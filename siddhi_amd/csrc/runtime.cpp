@@ -132,6 +132,14 @@ struct DevOut {
   bool rows;
   int64_t base;
   int arity = 2;        // uint32 words per tuple of hp (a filter's rows: 1)
+  bool logic = false;   // the logical pair's triples (e1, e2, e3): the trigger is the later of e2 / e3, and a member
+                        // that `or` left unbound is the word 0x80000000
+  // the trigger of output k, relative to base: its last event
+  uint32_t trigger(size_t k) const {
+    const uint32_t* tp = hp + (size_t)arity * k;
+    if (!logic) return tp[arity - 1];
+    return (uint32_t)std::max((int32_t)tp[1], (int32_t)tp[2]);
+  }
   const int64_t* hw = nullptr;  // compact form: one 64-bit word per value ...
   const uint8_t* hn = nullptr;  // ... and one byte of null flags per output (bit a: value a)
   // segments still in flight (round 5): outputs [seg_end[i-1], seg_end[i]) are in host memory once seg_ev[i] has
@@ -478,6 +486,21 @@ bool nand_progs_ok(const CompiledQuery& cq) {
       if (!(in.b == 0 || in.b == -1)) return false;
       const int sb = 3 - cq.fast_nand_slot3;  // slots 1 and 2 are the two operands'
       if (m == 0 ? in.a != 0 : m == 1 ? in.a != sb : !(in.a == 0 || in.a == cq.fast_nand_slot3)) return false;
+    }
+  return true;
+}
+
+// The logical pair (fast_pat_logic): c1 reads slot 0, c2 slot 0 and e2's slot, c3 slot 0 and e3's slot, one event
+// each; the same check otherwise.
+bool logic_progs_ok(const CompiledQuery& cq) {
+  const Instr* code = (const Instr*)(cq.blob.data() + cq.hdr.off_code);
+  for (int m = 0; m < 3; ++m)
+    for (int i = 0; i < cq.fast_logic_len[m]; ++i) {
+      const Instr& in = code[cq.fast_logic_off[m] + i];
+      if (in.op == OP_TS || in.op == OP_COL) return false;
+      if (in.op != OP_VAR) continue;
+      if (!(in.b == 0 || in.b == -1)) return false;
+      if (!(in.a == 0 || (m > 0 && in.a == cq.fast_logic_slot[m]))) return false;
     }
   return true;
 }
@@ -1269,6 +1292,11 @@ void read_outputs(sm_app* a, int qidx, const void* dev, int64_t n, std::vector<H
       h.tuple = rf + cq.hdr.nrefs_vis;
       h.e1 = h.tuple[0];
       h.e2 = h.tuple[cq.match_arity() - 1];
+    } else if (cq.fast_pat_logic) {  // three hidden refs (e1, e2, e3); the completing member is the later of e2 / e3,
+                                     // and a member `or` left unbound is -1
+      h.tuple = rf + cq.hdr.nrefs_vis;
+      h.e1 = h.tuple[0];
+      h.e2 = std::max(h.tuple[1], h.tuple[2]);
     } else if (cq.fast_every_within || cq.fast_seq_adjacent || cq.fast_pat_ms || cq.fast_pat_nand) {  // two hidden refs: (e1, e2)
       h.e1 = rf[cq.hdr.nrefs_vis];
       h.e2 = rf[cq.hdr.nrefs_vis + 1];
@@ -1581,7 +1609,9 @@ void nfa_outs_to_device(sm_app* a, QueryRt& q, std::vector<HostOut>& outs, int64
     if (outs[k].r.pos < nc || outs[k].e1 < 0 || outs[k].e2 < 0 || (ar > 2 && !outs[k].tuple))
       throw std::runtime_error("query '" + q.cq.name + "': internal error in the hand-over of carried partials");
     if (ar > 2) {
-      for (size_t m = 0; m < ar; ++m) pairs[ar * k + m] = (uint32_t)(outs[k].tuple[m] - ordinal_base);
+      for (size_t m = 0; m < ar; ++m)  // (an unbound member of the logical `or`: the null word)
+        pairs[ar * k + m] = q.cq.fast_pat_logic && outs[k].tuple[m] < 0 ? 0x80000000u
+                                                                        : (uint32_t)(outs[k].tuple[m] - ordinal_base);
     } else if (ar == 1) {  // the timeout: e1 alone
       pairs[k] = (uint32_t)(outs[k].e1 - ordinal_base);
     } else {
@@ -1725,7 +1755,13 @@ int64_t nfa_device_batch(sm_app* a, int qi, int s, size_t n, const int64_t* d_ts
 // partial's life is one event, so the state is a function of the last k - 1 events). The k-state pattern over several
 // streams (fast_pat_k, path 10) carries rows of the same form, the events its open partials have bound, each once:
 // replayed in (key, ordinal) order they bind again what they bound (S1 is none of S2 .. S(k-1), so none of them opens a
-// partial twice) and emit nothing, since no ek is among them; its partial table is dropped with the rows. The playback
+// partial twice) and emit nothing, since no ek is among them; its partial table is dropped with the rows. So does the
+// logical pair (fast_pat_logic, path 13). `and`: the replayed events bind again what they bound: an e2 / e3 event that
+// passes its condition against an earlier carried e1 of its key is that partial's first such event, or the partial
+// would hold an earlier one, which is then carried and replayed in front of it; A is neither B nor C, so no replayed
+// member opens a partial; nothing is emitted, since a partial holding both members has left the carry. `or`: the
+// events are e1 rows only; with A = B or A = C a replayed later row did not pass c2 / c3 against a carried earlier
+// one of its key, or that one would have matched and left the carry (path 12's argument). The playback
 // clock is left alone, as in nfa_device_batch. The caller's event-index arrays (d_ev_*, d_adv_*) are overwritten.
 void mseq_replay_carry(sm_app* a, int qi, hipStream_t hs) {
   QueryRt& q = *a->queries[qi];
@@ -1935,7 +1971,7 @@ void device_outputs(sm_app* a, int qi, hipStream_t hs, std::vector<DevOut>& outs
     pair_project((const uint32_t*)q.dev_pairs.p + ar * k0, c, (const NfaStream*)q.proj_desc_dev.p,
                  q.proj_ord, q.proj_n, q.proj_base, q.proj_ts, (const int64_t*)q.prev_carry.p, q.prev_carry_n,
                  q.prev_carry_w, (const char*)q.blob.p, compact ? nullptr : (DVal*)dvals, dts, a->sc, hs, rows, dw, dn,
-                 ck, ci, !defer, ar);
+                 ck, ci, !defer, ar, cq.fast_pat_logic ? cq.fast_logic_slot : nullptr);
     if (compact) {
       SM_HIP(hipMemcpyAsync(hvals + (size_t)k0 * ns * 8, dw, (size_t)c * ns * 8, hipMemcpyDeviceToHost, hs));
       SM_HIP(hipMemcpyAsync(hvals + (size_t)m * ns * 8 + k0, dn, (size_t)c, hipMemcpyDeviceToHost, hs));
@@ -1952,6 +1988,7 @@ void device_outputs(sm_app* a, int qi, hipStream_t hs, std::vector<DevOut>& outs
   }
   if (!defer) SM_HIP(hipStreamSynchronize(hs));
   DevOut d{qi, m, hp, compact ? nullptr : (const DVal*)hvals, hts, rows, q.proj_base, ar};
+  d.logic = cq.fast_pat_logic != 0;
   if (compact) {
     d.hw = (const int64_t*)hvals;
     d.hn = (const uint8_t*)(hvals + (size_t)m * ns * 8);
@@ -1991,10 +2028,17 @@ void materialize(sm_app* a, const DevOut& d, std::vector<HostOut>& outs) {
     for (size_t k = lo; k < hi; ++k) {
       const uint32_t* tp = d.hp + (size_t)d.arity * k;  // slot s of the match = word s (a filter: its row)
       const int64_t e1 = d.base + (int32_t)tp[0];
-      const int64_t e2 = d.base + (int32_t)tp[d.arity - 1];
+      const int64_t e2 = d.base + (int32_t)d.trigger(k);
       int64_t* rf = hrf + k * nr;
-      for (int r = 0; r < nr; ++r)
+      for (int r = 0; r < nr; ++r) {
+        if (d.logic) {  // word w holds slot fast_logic_slot[w]; an unbound member has no ordinal
+          const int sl = rslots[2 * r];
+          const uint32_t w = tp[sl == 0 ? 0 : sl == cq.fast_logic_slot[1] ? 1 : 2];
+          rf[r] = w == 0x80000000u ? -1 : d.base + (int32_t)w;
+          continue;
+        }
         rf[r] = d.arity > 2 ? d.base + (int32_t)tp[rslots[2 * r]] : rslots[2 * r] == 0 ? e1 : e2;
+      }
       HostOut& h = outs[base + k];
       memset(&h.r, 0, sizeof(h.r));
       h.r.pos = e2;
@@ -2029,7 +2073,7 @@ void deliver_direct(sm_app* a, const DevOut& d) {
   }
   const size_t m = (size_t)d.m;
   const size_t ar = (size_t)d.arity;
-  auto trig = [&](size_t k) { return d.hp[ar * k + ar - 1]; };
+  auto trig = [&](size_t k) { return d.logic ? d.trigger(k) : d.hp[ar * k + ar - 1]; };
   // the call's only outputs: the uniform chunk form (Pending::starts); otherwise PreparedChunks after what is there
   const bool uni = pd.chunks.empty() && !pd.uniform && pd.evs.size() == 0;
   if (!uni) pd.expand();
@@ -2878,7 +2922,9 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
 // carried from an earlier batch projected from prev_carry) or the logical absent `every e1=A -> not B and e3=C within T`
 // (CompiledQuery::fast_pat_nand, fast_pat_nand, path 12: (e1, e3) pairs as path 9's; its app is @app:playback, and once
 // the batch has succeeded a->clock advances to the largest event time of the feed's rows, as path 11 advances it, so
-// that a later hand-over starts from the right clock). `nst` are the host copies of the batch's stream
+// that a later hand-over starts from the right clock) or the logical pair `every e1=A -> e2=B and|or e3=C within T`
+// (CompiledQuery::fast_pat_logic, fast_pat_logic, path 13: (e1, e2, e3) triples in dev_pairs, carried members projected
+// from prev_carry, the carried events, as path 10's). `nst` are the host copies of the batch's stream
 // descriptors, already uploaded to d_streams. Returns the number of matches (the projection state set as in
 // device_batch_stream; the outputs that have consumers appended to draw), or FAST_OUTSIDE / FAST_NON_MONOTONE with
 // nothing changed.
@@ -2889,7 +2935,8 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
   const CompiledQuery& cq = q.cq;
   const bool pat = cq.fast_pat_ms;
   const bool nand = cq.fast_pat_nand;
-  const int s0 = nand ? cq.fast_nand_stream[0] : pat ? cq.fast_pat_stream[0] : cq.streams.at(0);
+  const bool logic = cq.fast_pat_logic != 0;
+  const int s0 = logic ? cq.fast_logic_stream[0] : nand ? cq.fast_nand_stream[0] : pat ? cq.fast_pat_stream[0] : cq.streams.at(0);
   const NfaStream& d = nst[s0];
   const char* blob = (const char*)q.blob.p;
   a->sc.used = 0;
@@ -2906,9 +2953,20 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
   MPatPlan pp;
   MPatKPlan kp;
   PNandPlan np;
+  PLogPlan lp;
   const int patk = cq.fast_pat_k;
   std::vector<int> read;  // the streams the query reads
-  if (nand) {
+  if (logic) {
+    lp.land = cq.fast_pat_logic == 1;
+    for (int m = 0; m < 3; ++m) {
+      lp.stream[m] = cq.fast_logic_stream[m];
+      lp.off[m] = cq.fast_logic_off[m];
+      lp.len[m] = cq.fast_logic_len[m];
+    }
+    lp.within = cq.fast_logic_within;
+    for (int m = 0; m < 3; ++m)
+      if (std::find(read.begin(), read.end(), lp.stream[m]) == read.end()) read.push_back(lp.stream[m]);
+  } else if (nand) {
     for (int m = 0; m < 3; ++m) {
       np.stream[m] = cq.fast_nand_stream[m];
       np.off[m] = cq.fast_nand_off[m];
@@ -2944,12 +3002,12 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
     }
     read = cq.streams;
   }
-  MSeqKeys& keys = nand ? static_cast<MSeqKeys&>(np) : patk ? static_cast<MSeqKeys&>(kp) : pat ? static_cast<MSeqKeys&>(pp) : sp;
+  MSeqKeys& keys = logic ? static_cast<MSeqKeys&>(lp) : nand ? static_cast<MSeqKeys&>(np) : patk ? static_cast<MSeqKeys&>(kp) : pat ? static_cast<MSeqKeys&>(pp) : sp;
   keys.keyed = cq.partition >= 0;
   for (int s : read) {  // every read stream's own key attribute
     keys.read |= 1ull << s;
     if (!keys.keyed) continue;
-    const int c = (nand ? cq.fast_nand_keycol : patk ? cq.fast_patk_keycol : pat ? cq.fast_pat_keycol : cq.fast_ms_keycol).at(s);
+    const int c = (logic ? cq.fast_logic_keycol : nand ? cq.fast_nand_keycol : patk ? cq.fast_patk_keycol : pat ? cq.fast_pat_keycol : cq.fast_ms_keycol).at(s);
     keys.kcol[s] = d_cols[c];
     if (d.types[c] == T_LONG) keys.wide |= 1ull << s;
   }
@@ -2963,8 +3021,9 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
   };
   // a sequence: k words per match, at most one match per event; the pattern: (e1, e2) per match, at most one per partial
   // the k-state pattern: k words per match, at most one per partial
-  const int64_t cap = patk ? (int64_t)n + q.carry.pn : pat || nand ? (int64_t)n + q.carry.n : (int64_t)n;
-  q.dev_pairs.ensure(std::max<size_t>(patk ? (size_t)cap * 4 * (size_t)patk : pat || nand ? (size_t)cap * 8 : n * 4 * (size_t)sp.k, 16));
+  // the logical pair: three words per match, at most one per partial
+  const int64_t cap = patk || logic ? (int64_t)n + q.carry.pn : pat || nand ? (int64_t)n + q.carry.n : (int64_t)n;
+  q.dev_pairs.ensure(std::max<size_t>(logic ? (size_t)cap * 12 : patk ? (size_t)cap * 4 * (size_t)patk : pat || nand ? (size_t)cap * 8 : n * 4 * (size_t)sp.k, 16));
   FastTimings* tm = a->fast_timing ? &a->fast_tm : nullptr;
   // the logical absent: build_event_index's clock_out alone, the largest event time of the feed's rows (heartbeats and
   // unread rows included) or the clock before it. One reduction in front of the driver, in stream order; its value is
@@ -2976,6 +3035,8 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
     a->sc.used = 0;  // (the driver's kernels follow the reduction on the stream)
   }
   auto closed = [&] {
+    if (logic)
+      return fast_pat_logic(fa, d_stream_idx, lp, d.nattr, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, cap, a->sc, hs, tm);
     if (nand)
       return fast_pat_nand(fa, d_stream_idx, np, d.nattr, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, cap, a->sc, hs, tm);
     if (patk)
@@ -3385,7 +3446,8 @@ void flush(sm_app* a) {
     // (paths 8 and 9)
     for (size_t qi = 0; qi < a->queries.size(); ++qi) {
       QueryRt& q = *a->queries[qi];
-      if (!(q.cq.fast_seq_ms || q.cq.fast_pat_ms || q.cq.fast_pat_k || q.cq.fast_absent || q.cq.fast_pat_nand) ||
+      if (!(q.cq.fast_seq_ms || q.cq.fast_pat_ms || q.cq.fast_pat_k || q.cq.fast_absent || q.cq.fast_pat_nand ||
+            q.cq.fast_pat_logic) ||
           q.nfa_mode || q.nfa_used ||
           !q.carry.active)
         continue;
@@ -3963,9 +4025,10 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
     // And its k-state sibling (CompiledQuery::fast_pat_k, path 10).
     // And the timeout `every e1=A -> not B for W` (CompiledQuery::fast_absent, path 11).
     // And the logical absent `every e1=A -> not B and e3=C within T` (CompiledQuery::fast_pat_nand, path 12).
+    // And the logical pair `every e1=A -> e2=B and|or e3=C within T` (CompiledQuery::fast_pat_logic, path 13).
     if (a->queries.size() == 1 &&
         (a->queries[0]->cq.fast_seq_ms > 0 || a->queries[0]->cq.fast_pat_ms || a->queries[0]->cq.fast_pat_k > 0 ||
-         a->queries[0]->cq.fast_absent || a->queries[0]->cq.fast_pat_nand) &&
+         a->queries[0]->cq.fast_absent || a->queries[0]->cq.fast_pat_nand || a->queries[0]->cq.fast_pat_logic) &&
         a->streams.size() <= 64)
       msq = a->queries[0].get();
     size_t need = batch_scratch(a, N);
@@ -3983,8 +4046,9 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
       // checks that before anything changes)
       if (msq->cq.fast_absent) need += nc * 8 + n * 16 + (size_t)msq->abs_inst.n * 64;
       // the k-state pattern: result, kept and k - 1 members per row and carried partial, a flag per event, k words and
-      // two sort pairs per tuple, the new partials (fast_pat_k checks the last two once they are counted)
-      if (const size_t k = (size_t)msq->cq.fast_pat_k) {
+      // two sort pairs per tuple, the new partials (fast_pat_k checks the last two once they are counted). The logical
+      // pair: the same with k = 3 (three members per row; fast_pat_logic makes the same checks)
+      if (const size_t k = (size_t)msq->cq.carry_parts_k()) {
         const size_t pn = (size_t)msq->carry.pn;
         need += (n + pn) * (4 * (k + 1) + 4 * k + 16 + 8 * (k + 1)) + n + nc;
       }
@@ -4011,6 +4075,7 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
         if (ms_tuples && !q.nfa_mode && !q.nfa_used &&
             (pat ? run_progs_ok(cq, cq.fast_pat_off, cq.fast_pat_len, 2)
                  : cq.fast_pat_nand ? nand_progs_ok(cq)
+                 : cq.fast_pat_logic ? logic_progs_ok(cq)
                  : cq.fast_absent ? run_progs_ok(cq, cq.fast_abs_off, cq.fast_abs_len, 2)
                  : cq.fast_pat_k ? run_progs_ok(cq, cq.fast_patk_off, cq.fast_patk_len, cq.fast_pat_k)
                                  : run_progs_ok(cq, cq.fast_ms_off, cq.fast_ms_len, cq.fast_seq_ms))) {
@@ -4187,7 +4252,8 @@ int sm_app_snapshot(sm_app* a, uint8_t* buf, size_t cap, size_t* len) {
           w.raw(rows.data(), rows.size() * 8);
         }
       }
-      if (q.cq.fast_pat_k) {  // the open partials of the k-state pattern (the rows above: the events they hold)
+      if (q.cq.carry_parts_k()) {  // the open partials of the k-state pattern and of the logical pair (the rows above:
+                                   // the events they hold)
         w.put<int64_t>(q.carry.pn);
         w.put<int32_t>(q.carry.pw);
         if (q.carry.pn > 0) {
@@ -4331,10 +4397,10 @@ int sm_app_restore(sm_app* a, const uint8_t* buf, size_t len) {
           q.abs_inst.n = ni;
         }
       }
-      if (q.cq.fast_pat_k) {
+      if (const int pk = q.cq.carry_parts_k()) {
         const int64_t pn = r.get<int64_t>();
         const int32_t pw = r.get<int32_t>();
-        if (pn < 0 || (pn > 0 && pw != q.cq.fast_pat_k + 1))
+        if (pn < 0 || (pn > 0 && pw != pk + 1))
           throw std::runtime_error("CannotRestoreSiddhiAppStateException: bad carry");
         if (pn > 0) {
           std::vector<int64_t> rows((size_t)pn * pw);
@@ -4353,8 +4419,11 @@ int sm_app_restore(sm_app* a, const uint8_t* buf, size_t len) {
           };
           for (int64_t c = 0; c < pn; ++c) {
             const int64_t* pr = rows.data() + c * pw;
-            bool ok = pr[1] >= 1 && pr[1] < q.cq.fast_pat_k;
-            for (int64_t i = 0; ok && i < pr[1]; ++i) ok = held(pr[0], pr[2 + i]);
+            // the logical pair: state 1 holds e1, 2 and 3 hold e1 and one of e2 / e3; `or` has state 1 only
+            const bool lg = q.cq.fast_pat_logic != 0;
+            bool ok = pr[1] >= 1 && (lg ? pr[1] <= (q.cq.fast_pat_logic == 1 ? 3 : 1) : pr[1] < pk);
+            const int64_t nheld = lg ? (pr[1] == 1 ? 1 : 2) : pr[1];
+            for (int64_t i = 0; ok && i < nheld; ++i) ok = held(pr[0], pr[2 + i]);
             if (!ok) throw std::runtime_error("CannotRestoreSiddhiAppStateException: bad carry");
           }
           q.carry.reserve_parts(pn, pw, a->stream);
@@ -4692,7 +4761,7 @@ int sm_app_device_project(sm_app* a, const char* query_name, sm_dval* d_values, 
     pair_project((const uint32_t*)q->dev_pairs.p, m, (const NfaStream*)q->proj_desc_dev.p, q->proj_ord, q->proj_n,
                  q->proj_base, q->proj_ts, (const int64_t*)q->prev_carry.p, q->prev_carry_n, q->prev_carry_w,
                  (const char*)q->blob.p, (DVal*)d_values, d_ts, a->sc, hs, q->cq.hdr.kind == 0, nullptr, nullptr, nullptr,
-                 nullptr, true, q->cq.match_arity());
+                 nullptr, true, q->cq.match_arity(), q->cq.fast_pat_logic ? q->cq.fast_logic_slot : nullptr);
   });
 }
 

@@ -29,6 +29,10 @@ fast_timing. Each step starts from a fresh runtime state (option reset), as benc
                                                         # within 1 sec` on a three-way stream index, @app:playback:
                                                         # fast_path 12 (kernels/mpat_nand_dev.h); routes as for --query
                                                         # streams
+    python tools/seq_bench.py --query logic_and ...         # the logical pair `every e1=A[c1] -> e2=B[c2] and e3=C[c3]
+                                                        # within 1 sec` on the same three-way stream index, and with
+                                                        # --query logic_or its `or` form: fast_path 13
+                                                        # (kernels/mpat_logic_dev.h); routes as for --query streams
 
 Step time is a host clock around work that ends in a device synchronise; a run without a GPU fails."""
 import argparse
@@ -68,7 +72,13 @@ QUERY_ABSENT_AND = ("@info(name='q') from every e1=A[price>20] -> not B[price>70
                     "select e1.timestamp as i, e3.timestamp as j insert into OutputStream;")
 
 
-STREAM_QUERIES = ("streams", "streams3", "pattern_streams", "pattern_chain", "absent", "absent_and")
+QUERY_LOGIC = ("@info(name='q') from every e1=A[price>20] -> e2=B[price>e1.price] {op} e3=C[price<e1.price] within 1 sec "
+               "select e1.timestamp as i, e2.timestamp as j, e3.timestamp as l insert into OutputStream;")
+
+
+STREAM_QUERIES = ("streams", "streams3", "pattern_streams", "pattern_chain", "absent", "absent_and", "logic_and",
+                  "logic_or")
+THREE_WAY = ("absent_and", "logic_and", "logic_or")  # queries on the three-way stream index
 
 
 def apps(query, cancel_above="70"):
@@ -78,6 +88,10 @@ def apps(query, cancel_above="70"):
         q = QUERY_ABSENT_AND.replace("price>70", "price>" + cancel_above)
         return {"keyed": head + "partition with (symbol of A, symbol of B, symbol of C) begin " + q + " end;",
                 "unkeyed": head + q}
+    if query in ("logic_and", "logic_or"):
+        q = QUERY_LOGIC.format(op=query[6:])
+        return {"keyed": SCHEMA_ABC + "partition with (symbol of A, symbol of B, symbol of C) begin " + q + " end;",
+                "unkeyed": SCHEMA_ABC + q}
     if query in STREAM_QUERIES:
         q = {"streams": QUERY_AB, "streams3": QUERY_ABA, "pattern_streams": QUERY_PAT_AB,
              "pattern_chain": QUERY_PAT_ABA, "absent": QUERY_ABSENT}[query]
@@ -100,6 +114,8 @@ LABELS += ["absent_facts", "absent_pack", "absent_sort", "absent_next", "absent_
            "absent_inst", "absent_emit", "absent_order", "absent_project", "absent_carry"]
 LABELS += ["pnand_facts", "pnand_pack", "pnand_sort", "pnand_next", "pnand_link", "pnand_count", "pnand_scan", "pnand_emit",
            "pnand_order", "pnand_carry", "pnand_clock"]
+LABELS += ["plog_facts", "plog_pack", "plog_sort", "plog_link", "plog_count", "plog_scan", "plog_cand", "plog_emit",
+           "plog_order", "plog_parts", "plog_carry"]
 
 
 def precompile(query, cancel_above):
@@ -138,7 +154,7 @@ def main():
     ap.add_argument("--route", choices=["closed", "nfa"], default="closed")
     ap.add_argument("--forms", default="keyed,unkeyed")
     ap.add_argument("--query", choices=["pair", "three", "streams", "streams3", "pattern_streams", "pattern_chain", "absent",
-                                        "absent_and"],
+                                        "absent_and", "logic_and", "logic_or"],
                     default="pair")
     ap.add_argument("--cancel-above", default="70",
                     help="--query absent_and: the constant of c2 `not B[price>X]`; the outputs a large X adds are the "
@@ -170,7 +186,7 @@ def main():
         x = ordinals * (0x9E3779B97F4A7C15 - (1 << 64))  # (wraps: a multiply-xorshift hash, one bit of it)
         x = (x ^ (x >> 29)) * (0xBF58476D1CE4E5B9 - (1 << 64))
         sidx = ((x >> 43) & 1).to(torch.int32)
-        if a.query == "absent_and":  # three ways: two more bits of the hash, folded to 0 .. 2
+        if a.query in THREE_WAY:  # three ways: two more bits of the hash, folded to 0 .. 2
             sidx = (((x >> 41) & 0xFFFF) % 3).to(torch.int32)
     hs = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     build_id = _lib.lib().sm_build_id().decode()
