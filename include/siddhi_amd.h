@@ -248,6 +248,16 @@ int sm_app_process_device_batch(sm_app* app, const char* stream_id, size_t n, co
  * that completing event, then e1, and carry its timestamp. It carries the open partials, an `and` partial possibly with
  * one member bound, with the events they hold, and hands over to the NFA kernel as the k-state pattern does. Without
  * a `within` the query runs on the NFA kernel.
+ * The count pattern `every e1=A[c1] -> e2=B[c2]<m:n> -> e3=C[c3] within T` (A, B and C three different streams of one
+ * schema, 0 <= m <= n, 1 <= n <= 6, c2 reading e1 and the current e2, c3 reading e1 and e3, the select reading e1, e2[k]
+ * with k < n, e2[last] and e3, no having; partitioned: each read stream keyed by one INT / LONG attribute of its own) runs
+ * a closed form too under the same conditions ("fast_path:<query>" = 14, "match_arity:<query>" = n + 2: tuples
+ * (e1, e2[0] .. e2[n-1], e3)): every A event passing c1 binds the first n later B events of its partition instance passing
+ * c2; once it holds m of them, the first C event of the instance ends it: beyond T of the hit bound last (of e1 when none
+ * is bound) the partial is dead, otherwise it is emitted if the event passes c3, with the event's timestamp. The outputs
+ * come in order of e3, then the m-th hit (e1 when m = 0), then e1. It carries the open partials with the events they
+ * hold (a partial below m hits has no clock: the carry is bounded by the data, and by the scratch memory, beyond which the
+ * NFA kernel takes the query over) and hands over to the NFA kernel as the k-state pattern does.
  * "output_events:<query>" (sm_app_get_stat) = output events of the last such batch; "nfa_kernel:<query>" = which NFA
  * kernel ran it (1 = query-specialised, 2 = interpreter, 0 = none yet). */
 int sm_app_process_device_events(sm_app* app, size_t n, const int32_t* d_stream_idx, const int64_t* d_timestamps,
@@ -332,7 +342,8 @@ int sm_order_outputs(const void* d_recs, size_t n, size_t stride, void* d_out, v
  * the stat "match_arity:<query>". Members carried from an earlier batch are negative as int32. The logical pair
  * ("fast_path" 13) has three words per tuple, (e1, e2, e3) in the order of the query text, in order of the later of e2 /
  * e3; a member that `or` left unbound is the word 0x80000000, which no carried member is (a carried member's ordinal lies
- * less than 2^31 below the batch's base). */
+ * less than 2^31 below the batch's base). The count pattern ("fast_path" 14) has n + 2 words per tuple,
+ * (e1, e2[0] .. e2[n-1], e3), in order of e3; a hit slot that is not bound is the word 0x80000000 likewise. */
 int sm_app_device_matches(sm_app* app, const char* query_name, const uint32_t** d_pairs, size_t* n);
 /* The same tuples (match_arity uint32 words each; a filter query's kept rows: one) copied into a caller-owned device
  * buffer of cap_bytes on hip_stream (asynchronous); *n = tuples. Lets a caller hand them to its own collectives. */
@@ -352,7 +363,8 @@ typedef struct sm_dval {
  * last device batch of a query: output k (the k-th tuple of sm_app_device_matches, or a filter query's k-th kept
  * row) gets its select list in d_values[k * nsel .. k * nsel + nsel) and its timestamp (the last event's time,
  * StateEvent.timestamp) in d_ts[k] (d_ts may be NULL; the logical pair: the time of the later of e2 / e3, and the
- * attributes of a member `or` left unbound come out with is_null = 1). An e1 carried from an earlier batch is read from
+ * attributes of a member `or` left unbound come out with is_null = 1; the count pattern: e3's time, the attributes of a hit
+ * slot that is not bound come out with is_null = 1, and e2[last] is the last bound slot). An e1 carried from an earlier batch is read from
  * the carried partial; a batch the NFA kernel took returns the values the kernel evaluated. With d_values == NULL only *n and
  * *nsel are set. The batch's columns, event times and ordinals are read again: call it before freeing them.
  * SM_E_UNSUPPORTED when the query's last outputs came from host-API events (they reach the callbacks). */
@@ -369,10 +381,14 @@ int sm_app_device_project(sm_app* app, const char* query_name, sm_dval* d_values
  * mpat_count, mpat_scan, mpat_emit, mpat_order, mpat_carry), the k-state pattern 10 (labels mpatk_*), the timeout 11
  * (labels absent_*), the logical absent 12 (labels pnand_*), the logical pair `and` / `or` 13 (labels plog_facts,
  * plog_pack, plog_sort, plog_link, plog_count, plog_scan, plog_cand, plog_emit, plog_order, plog_parts, plog_carry),
+ * the count pattern 14 (labels pcnt_facts, pcnt_pack, pcnt_sort, pcnt_link, pcnt_count, pcnt_scan, pcnt_cand, pcnt_emit,
+ * pcnt_order, pcnt_parts, pcnt_carry),
  * 5 = general NFA kernel;
  * filter queries 3 = filter interpreter, 4 = typed conjunction. "output_events:<query>" = its output count.
  * "match_arity:<query>" = uint32 words per tuple of sm_app_device_matches: k for a k-state sequence of the adjacent-run
- * form, 3 for the logical pair, 2 for every other pattern or sequence, 1 for a filter (its kept row).
+ * form, 3 for the logical pair, n + 2 for the count pattern, 2 for every other pattern or sequence, 1 for a filter (its kept row).
+ * "carry_partials:<query>" = the open partials the closed forms with a partial table carry after the last batch (paths
+ * 10, 13, 14); "carry_unclocked:<query>" = those of the count pattern's that hold fewer than m hits, which no window ends.
  * "kernel_ms:<label>" / "kernel_calls:<label>" and "fast_ms:group" / "fast_ms:walk" / "fast_ms:order" (per-kernel
  * and phase times in ms; need the "fast_timing" option). "nfa_state:<query>" = 1 once a closed-form query's matching
  * state is held by the general NFA kernel for good: host events it could not take on the closed form (a null value,

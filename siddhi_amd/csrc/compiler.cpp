@@ -1104,6 +1104,84 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
         }
       }
     }
+    // ---- the count pattern: every e1=A[c1] -> e2=B[c2]<m:n> -> e3=C[c3] within T over three different streams of one
+    // schema, 0 <= m <= n, 1 <= n <= 6 (kernels/mpat_count_dev.h). The within on the last element is part of the form, as
+    // on paths 12 and 13, and there is none elsewhere. c2 reads e1 and the current e2 (no e2[k], no e2[last]), c3 reads
+    // e1 and e3: a hit depends on e1 alone, so the hits of a partial are the first n rows passing c2. The select reads
+    // e1, e2[k] with k < n, e2[last] and e3. A, B and C are pairwise different: the hand-over replays held events on
+    // their own streams, and a replayed hit or e1 on another element's stream would bind or open a second time
+    std::vector<const StateElem*> cel;  // the chain's elements, whichever way its `->` nodes nest
+    {
+      bool flat = q.input == InputKind::PATTERN && !q.having;
+      std::function<void(const StateElem*)> walk = [&](const StateElem* el) {
+        if (el->kind == StateKind::NEXT) {
+          if (el->has_within) flat = false;  // a parenthesised sub-chain with its own within
+          walk(el->a.get());
+          walk(el->b.get());
+        } else {
+          cel.push_back(el);
+        }
+      };
+      if (flat && root_el->kind == StateKind::NEXT) walk(root_el);
+      if (!flat) cel.clear();
+    }
+    if (cel.size() == 3 && cel[0]->kind == StateKind::EVERY && !cel[0]->has_within &&
+        cel[0]->a->kind == StateKind::STREAM && !cel[0]->a->has_within && cel[1]->kind == StateKind::COUNT &&
+        !cel[1]->has_within && cel[1]->a->kind == StateKind::STREAM && !cel[1]->a->has_within &&
+        cel[2]->kind == StateKind::STREAM && cel[2]->has_within && cel[2]->within_ms >= 0 && (int)pres.size() == 3 &&
+        h.nslots == 3) {
+      const StateElem* ce = cel[1];
+      const int mn = ce->min_count == kAny ? 0 : ce->min_count;
+      const int mx = ce->max_count == kAny ? INT32_MAX : ce->max_count;
+      bool ok = mn >= 0 && mn <= mx && mx >= 1 && mx <= 6 && pres[0].kind == PK_STREAM && pres[1].kind == PK_COUNT &&
+                pres[2].kind == PK_STREAM && pres[0].stateId == 0 && pres[1].stateId == 1 && pres[2].stateId == 2 &&
+                pres[1].minCount == mn && pres[1].maxCount == mx;
+      for (size_t r = 0; ok && r < refs.size(); r += 2) {
+        const int sl = refs[r], ix = refs[r + 1];
+        if (sl == 1) ok = ix >= kCurrent && ix < mx;  // e2[k], e2[last] (the current event at the output)
+        else ok = (sl == 0 || sl == 2) && (ix == 0 || ix == kCurrent);
+      }
+      for (int m = 0; ok && m < 3; ++m)
+        for (int i = 0; ok && i < pres[m].progLen; ++i) {
+          const Instr& in = code[pres[m].progOff + i];
+          if (in.op == OP_TS || in.op == OP_COL) ok = false;
+          if (in.op != OP_VAR) continue;
+          if (in.a == 0) ok = in.b == 0 || in.b == kCurrent;
+          else if (in.a == m) ok = m == 1 ? in.b == kCurrent : (in.b == 0 || in.b == kCurrent);
+          else ok = false;
+        }
+      const int ss[3] = {ok ? lw.metas[0].stream : -1, ok ? lw.metas[1].stream : -1, ok ? lw.metas[2].stream : -1};
+      if (ok && (ss[0] == ss[1] || ss[0] == ss[2] || ss[1] == ss[2])) ok = false;
+      std::vector<int> keycol(app.streams.size(), -1);
+      for (int m = 0; ok && m < 3; ++m) {
+        const StreamDef& d0 = app.streams[ss[0]];
+        const StreamDef& d = app.streams[ss[m]];
+        ok = d.attrs.size() == d0.attrs.size();
+        for (size_t c = 0; ok && c < d.attrs.size(); ++c) ok = d.attrs[c].type == d0.attrs[c].type;
+        if (!ok || partition < 0) continue;
+        // partitioned: every read stream keyed by one INT / LONG attribute of its own
+        ok = false;
+        for (auto& w : app.partitions[partition].with)
+          if (w.stream_id == d.id && w.key->kind == ExprKind::VAR && w.key->stream_ref.empty()) {
+            const int c = d.index_of(w.key->attr);
+            if (c >= 0 && (d.attrs[c].type == AttrType::INT || d.attrs[c].type == AttrType::LONG)) {
+              keycol[ss[m]] = c;
+              ok = true;
+            }
+          }
+      }
+      if (ok) {
+        cq.fast_pat_count = mx;
+        cq.fast_count_min = mn;
+        cq.fast_count_keycol = keycol;
+        cq.fast_count_within = cel[2]->within_ms;
+        for (int m = 0; m < 3; ++m) {
+          cq.fast_count_stream[m] = ss[m];
+          cq.fast_count_off[m] = pres[m].progOff;
+          cq.fast_count_len[m] = pres[m].progLen;
+        }
+      }
+    }
   }
   h.npre = (int)pres.size();
   h.npost = (int)posts.size();
@@ -1122,6 +1200,11 @@ CompiledQuery compile_query(const App& app, const Query& q, int order, int parti
   if (cq.fast_pat_nand) refs.insert(refs.end(), {0, 0, cq.fast_nand_slot3, 0});  // hidden (e1, e3) ordinals, likewise
   if (cq.fast_pat_logic)  // hidden (e1, e2, e3) ordinals in the order of the query text, likewise
     refs.insert(refs.end(), {0, 0, cq.fast_logic_slot[1], 0, cq.fast_logic_slot[2], 0});
+  if (cq.fast_pat_count) {  // hidden (e1, e2[0] .. e2[n-1], e3) ordinals, likewise
+    refs.insert(refs.end(), {0, 0});
+    for (int k = 0; k < cq.fast_pat_count; ++k) refs.insert(refs.end(), {1, k});
+    refs.insert(refs.end(), {2, 0});
+  }
   h.nrefs = (int)refs.size() / 2;
   h.nconst = (int)consts.size();
   // per-key state layout (int64 words)

@@ -127,14 +127,32 @@ struct CompiledQuery {
   int fast_logic_slot[3] = {0, 0, 0};
   int64_t fast_logic_within = -1;
   std::vector<int> fast_logic_keycol;
-  // uint32 words per device match tuple: k, 3 for the logical pair, 2 for every other state query, 1 for a filter (its
-  // kept row) and for the timeout (its e1)
+  // fast path: every e1=A[c1] -> e2=B[c2]<m:n> -> e3=C[c3] within T over three different streams of one schema, 0 <= m
+  // <= n, 1 <= n <= 6, c2 reading e1 and the current e2, c3 reading e1 and e3, the select reading e1, e2[k] (k < n),
+  // e2[last] and e3, no having (pattern: every A event passing c1 binds the first n later B events of its partition
+  // instance passing c2; from the m-th on, the first later C event ends it: beyond T of the hit bound last (of e1 if
+  // none) the partial is dead, otherwise it emits if the event passes c3; kernels/mpat_count_dev.h). fast_pat_count = n
+  // (0: not this form), a mark of its own, which none of the other marks accompanies: such a query runs through the
+  // interleaved entry point only. fast_count_min = m; index 0, 1, 2 is e1, e2, e3: fast_count_stream their app streams (slot = index),
+  // fast_count_off / len their condition programs (state context), fast_count_within = T (always >= 0),
+  // fast_count_keycol[s] as fast_ms_keycol. The plan carries the hidden ordinal refs (e1, e2[0] .. e2[n-1], e3) after the
+  // visible ones; a hit slot that is not bound has no ordinal there.
+  int fast_pat_count = 0;
+  int fast_count_min = 0;
+  int fast_count_stream[3] = {0, 0, 0};
+  int fast_count_off[3] = {0, 0, 0}, fast_count_len[3] = {0, 0, 0};
+  int64_t fast_count_within = -1;
+  std::vector<int> fast_count_keycol;
+  // uint32 words per device match tuple: k, 3 for the logical pair, n + 2 for the count pattern, 2 for every other state
+  // query, 1 for a filter (its kept row) and for the timeout (its e1)
   int match_arity() const {
     return hdr.kind == 0 || fast_absent ? 1
-           : fast_seq_k ? fast_seq_k : fast_seq_ms ? fast_seq_ms : fast_pat_k ? fast_pat_k : fast_pat_logic ? 3 : 2;
+           : fast_seq_k ? fast_seq_k : fast_seq_ms ? fast_seq_ms : fast_pat_k ? fast_pat_k : fast_pat_logic ? 3
+           : fast_pat_count ? fast_pat_count + 2 : 2;
   }
   // the closed forms that carry an event table and a partial table of k + 1 words per row (FastCarry::parts): k, or 0
-  int carry_parts_k() const { return fast_pat_k ? fast_pat_k : fast_pat_logic ? 3 : 0; }
+  // (the count pattern: rows [key, hits | in-e3 << 8, tlast, p, o1, n hit ordinals], n + 5 words)
+  int carry_parts_k() const { return fast_pat_k ? fast_pat_k : fast_pat_logic ? 3 : fast_pat_count ? fast_pat_count + 4 : 0; }
 };
 
 struct CompiledPartition {

@@ -47,7 +47,7 @@ struct FastState {
   // pipeline of the last batch: 2 = sort / walk, 3 = bucket stack; seqpath.hip: 6 = adjacent pairs, 7 = adjacent runs,
   // 8 = adjacent runs over several streams, 9 = the pattern over two streams, 10 = the k-state pattern over several
   // streams, 11 = the timeout `every A -> not B for W`, 12 = the logical absent `every A -> not B and C within T`,
-  // 13 = the logical pair `every A -> B and|or C within T`
+  // 13 = the logical pair `every A -> B and|or C within T`, 14 = the count pattern `every A -> B<m:n> -> C within T`
   int last_path = 0;
 };
 
@@ -80,11 +80,12 @@ struct FastCarry {
   bool active = false;      // a device batch has run for this query: ts_last is valid
   int64_t ts_last = 0;      // event time of the last event of the last batch
   // fast_pat_k and fast_pat_logic only: the open partials [key, bound events s, global ordinals o1 .. os padded to
-  // k - 1], every key's in order of o1 (fast_pat_logic: [key, state, o1, o2], fastpath.h fast_pat_logic); `rows` are
-  // then the events they hold, each once, with the stream as the last word
+  // k - 1], every key's in order of o1 (fast_pat_logic: [key, state, o1, o2], fastpath.h fast_pat_logic; fast_pat_count:
+  // [key, hits | in-e3 << 8, tlast, p, o1, n hit ordinals], fastpath.h fast_pat_count); `rows` are then the events they
+  // hold, each once, with the stream as the last word
   int64_t* parts = nullptr;  // device, pn rows of pw words
   int64_t pn = 0, pcap = 0;
-  int pw = 0;               // k + 1
+  int pw = 0;               // k + 1 (fast_pat_count: n + 5)
   // second buffer of `rows` (spare_words words): the carry-out that writes each row once, in its place, writes there
   // while it reads the old rows, and the two change places (stack.hip build_carry_runs)
   int64_t* spare = nullptr;
@@ -268,6 +269,36 @@ int64_t fast_pat_logic(const FastArgs& a, const int32_t* sid, const PLogPlan& p,
                        FastCarry& carry, uint32_t* tuples_out, int64_t tuples_cap, Scratch& sc, hipStream_t s,
                        FastTimings* tm = nullptr);
 
+// The count pattern `every e1=A[c1] -> e2=B[c2]<m:n> -> e3=C[c3] within T` over three different streams of one schema
+// on an interleaved batch (seqpath.hip, mpat_count_dev.h has the rule and the kernels).
+struct PCntPlan : MSeqKeys {
+  int cmin = 0, cmax = 1;          // m, n: 0 <= m <= n, 1 <= n <= 6
+  int stream[3] = {0, 0, 0};       // app streams of A, B and C, pairwise different
+  int off[3] = {0, 0, 0}, len[3] = {0, 0, 0};  // c1 (over e1), c2 (over e1 and the current e2), c3 (over e1 and e3)
+  int64_t within = -1;             // T >= 0, against the hit bound last (e1 if none)
+};
+
+// a.st, `sid`, key_remap and FAST_KEY_SPAN as fast_seq_ms. Outputs are tuples of n + 2 words (e1, e2[0] .. e2[n-1], e3) as
+// fast_pat_k's (members carried from earlier batches negative as int32; a hit slot that is not bound is the word
+// 0x80000000, which no carried member is), in order of (e3, the m-th hit or e1 if m = 0, e1), at most n + carry.pn of
+// them (tuples_cap). The carry is fast_pat_k's two tables: the open partials (FastCarry::parts, rows
+// [key, hits | in-e3 << 8, tlast, p, o1, n hit ordinals], n + 5 words) and the events they hold. No window bounds the open
+// partials (one with fewer than m hits has no clock): they are bounded by the data, and by the scratch, which is checked
+// once they are counted and before anything changes (FAST_OUTSIDE), and by pcnt_carry_cap, likewise. Both error results
+// as fast_pat_k. Sets fs.last_path = 14.
+// The cap on the open partials a batch of n rows may leave: every batch's scratch is its per-row terms plus the constant
+// kBatchScratchSlack (runtime.cpp batch_scratch), and the carried state has to fit what the batch's own rows do not
+// claim: one partial per row, plus as many as the slack holds at the bytes a partial costs the carry-out (its row of
+// n + 5 words, and n + 1 held events at build_carry's 8 cw + 44 bytes each). It also bounds what the link pass spends on
+// carried partials that never complete (each is scanned again from the head of its key's run in every batch).
+constexpr size_t kBatchScratchSlack = (size_t)64 << 20;
+inline int64_t pcnt_carry_cap(int64_t n, int cmax, int cw) {
+  return n + (int64_t)(kBatchScratchSlack / ((size_t)(cmax + 1) * (size_t)(8 * cw + 44) + 8 * (size_t)(cmax + 5)));
+}
+int64_t fast_pat_count(const FastArgs& a, const int32_t* sid, const PCntPlan& p, int nattr, FastState& fs,
+                       FastCarry& carry, uint32_t* tuples_out, int64_t tuples_cap, Scratch& sc, hipStream_t s,
+                       FastTimings* tm = nullptr);
+
 // The hand-over of the instances to the NFA kernel: word `word` of the per-key state of slots 0 .. n - 1 (ks: word-major,
 // one column of state_slots per word) becomes create[slot], the instance's creation ordinal.
 void absent_set_creation(int64_t* ks, int64_t state_slots, int word, const int64_t* create, int64_t n, hipStream_t s);
@@ -326,9 +357,12 @@ void pair_project(const uint32_t* pairs, int64_t m, const NfaStream* st_dev, con
                   int64_t* words = nullptr, uint8_t* nulls = nullptr,  // words / nulls: compact form (nsel <= 8)
                   const uint32_t* carry_keys = nullptr, const uint32_t* carry_idx = nullptr, bool sync = true,
                   int arity = 2,  // arity k > 2: `pairs` are k-tuples (the adjacent-run closed form), slot s = word s
-                  const int* logic_slot = nullptr);  // the logical pair's triples: word w holds slot logic_slot[w], a
+                  const int* logic_slot = nullptr,   // the logical pair's triples: word w holds slot logic_slot[w], a
                                                      // word 0x80000000 is an absent member (its attributes are null),
                                                      // and ts_out is the event time of the later of e2 / e3
+                  bool count = false);  // the count pattern's tuples (e1, e2[0] .. e2[arity-3], e3): slot 1 is read at
+                                        // an index or at CURRENT (the last bound hit); a word 0x80000000 is a hit slot
+                                        // that is not bound (its attributes are null)
 // The carried partials' e1 ordinals sorted for pair_project (carry_keys / carry_idx, nc each, in sc): a caller
 // projecting one batch's outputs in several launches sorts them once (round 5: device_outputs' segments)
 void pair_project_carry_order(const int64_t* prev_carry, int64_t nc, int cw, int64_t base, Scratch& sc, hipStream_t s,

@@ -1,5 +1,5 @@
-// Host entries of the eight sequence closed forms (fastpath.h has their contracts, seq_dev.h / mseq_dev.h / mpat_dev.h /
-// mpatk_dev.h / absent_dev.h / mpat_nand_dev.h / mpat_logic_dev.h the rules and the kernels). Every driver runs one batch through the same stages, each written once below:
+// Host entries of the nine sequence closed forms (fastpath.h has their contracts, seq_dev.h / mseq_dev.h / mpat_dev.h /
+// mpatk_dev.h / absent_dev.h / mpat_nand_dev.h / mpat_logic_dev.h / mpat_count_dev.h the rules and the kernels). Every driver runs one batch through the same stages, each written once below:
 //   begin      Batch: the timing start, the scratch mark, and leave(), which every return goes through
 //   facts      one streaming pass over the keys, event times and ordinals, plus the carried ordinals; its read-back is
 //              the only host round trip before anything is changed (Facts: the same fields for SeqFacts and MSeqFacts)
@@ -40,10 +40,14 @@
 //   fast_pat_logic     path 13: path 10 with plog_link_kernel in place of its link pass: two members found independently,
 //                      both (and) or the earlier (or); three words per tuple and one stable sort by the completing member;
 //                      the carry is path 10's two tables
+//   fast_pat_count     path 14: path 13 with pcnt_link_kernel in place of its link pass: up to n hits, then the first C
+//                      row in e3 that dies or passes; n + 2 words per tuple and one stable sort by (e3, p); the carry
+//                      is path 10's two tables with rows of n + 5 words, bounded by the scratch and not by a window
 #include <string>
 
 #include "absent_dev.h"
 #include "fastpath.h"
+#include "mpat_count_dev.h"
 #include "mpat_dev.h"
 #include "mpat_logic_dev.h"
 #include "mpat_nand_dev.h"
@@ -168,6 +172,10 @@ constexpr Labels kAbsLabels = {"absent_facts", "absent_pack", "absent_sort",  nu
 constexpr Labels kPNandLabels = {"pnand_facts", "pnand_pack", "pnand_sort",  nullptr,
                                  "pnand_count", "pnand_scan", "pnand_emit",  "pnand_carry",
                                  "logical-absent pattern closed form"};
+
+constexpr Labels kPCntLabels = {"pcnt_facts", "pcnt_pack", "pcnt_sort",  "pcnt_cand",
+                                "pcnt_count", "pcnt_scan", "pcnt_emit",  "pcnt_carry",
+                                "count pattern closed form"};
 
 constexpr Labels kPLogLabels = {"plog_facts", "plog_pack", "plog_sort",  "plog_cand",
                                 "plog_count", "plog_scan", "plog_emit",  "plog_carry",
@@ -1598,6 +1606,186 @@ int64_t fast_pat_logic(const FastArgs& a, const int32_t* sid, const PLogPlan& p,
   carry.pn = pk;
   carry.pw = pw;
   return carry_out(b, a, o, ncand, nattr, h.ts_last, carry, fs, 13, L, m, false, sid);
+}
+
+int64_t fast_pat_count(const FastArgs& a, const int32_t* sid, const PCntPlan& p, int nattr, FastState& fs,
+                       FastCarry& carry, uint32_t* tuples_out, int64_t tuples_cap, Scratch& sc, hipStream_t s,
+                       FastTimings* tm) {
+  const Labels& L = kPCntLabels;
+  const int64_t n = a.n;
+  const int pw = p.cmax + 5, mw = p.cmax + 1, tw = p.cmax + 2;
+  if (n == 0) return 0;
+  const int64_t ne = carry.n, ncp = carry.pn;
+  if (n >= 0x7fffffffll || n + ncp >= 0x7fffffffll || n + ne >= 0x7fffffffll || p.within < 0 || p.cmin < 0 ||
+      p.cmin > p.cmax || p.cmax < 1 || p.cmax > kPCntMax || p.stream[0] == p.stream[1] || p.stream[0] == p.stream[2] ||
+      p.stream[1] == p.stream[2])
+    return FAST_OUTSIDE;
+  for (int m = 0; m < 3; ++m)
+    if (p.stream[m] < 0 || p.stream[m] >= kMSeqStreams) return FAST_OUTSIDE;
+  if (ncp > 0 && carry.pw != pw) return FAST_OUTSIDE;
+  const bool keyed = p.keyed;
+  Batch b(sc, s, tm, false);
+  const int cw = 4 + nattr;
+  const int64_t ntiles = (n + kSeqTile - 1) / kSeqTile;
+
+  MSeqSrc src = mseq_src(n, sid, p);
+  src.ts = a.ts;
+  src.ordinals = a.ordinals;
+  src.obase = a.ordinal_base;
+
+  uint32_t* tile_n;
+  const Facts h = mseq_facts(b, a, src, keyed, ntiles, carry, L.facts, &tile_n);
+  const int64_t np = h.np;
+  int kbits;
+  if (const int64_t r = envelope(h, true, keyed, np + ncp <= tuples_cap, carry, cw, p.remap_span, &kbits))
+    return b.leave(r);
+  if (np == 0) {  // no row of a stream the query reads: its carried partials wait
+    fs.last_path = 14;
+    return b.leave(0);
+  }
+  const bool wide = kbits > 32;
+
+  const int64_t cand_cap = np + ne;  // every read row and every carried event at most once
+  const int64_t total = ncp + n;     // entries of res / kept, rows of mid
+  const int64_t rtiles = (total + kSeqTile - 1) / kSeqTile;
+  const size_t hist = (size_t)8 << 20;
+  {  // scratch up to the counts, for the worst case, before anything changes
+    const size_t link = (size_t)np * (keyed ? (wide ? 27 : 19) : 6) + (size_t)total * (8 + 4 * mw) + (size_t)(ne + n) +
+                        (size_t)(ntiles + 2 * rtiles + 8) * 8 + hist;
+    if (sc.used + (size_t)cand_cap * 32 + link + 8192 > sc.cap) return b.leave(FAST_OUTSIDE);
+  }
+  uint32_t* npart = (uint32_t*)sc.take(8);  // the partials that stay
+  const Out o = take_out(sc, cand_cap);
+
+  const Rows rows = mseq_pack_sort(b, src, tile_n, ntiles, np, keyed, h.kmin, kbits, L);
+  b.event(1);
+
+  // ---- link: every partial (carried ones, then A rows passing c1) scans its key run for its hits and its e3
+  SM_HIP(hipMemsetAsync(o.ctl, 0, 8, s));
+  PCntArgs ma{};
+  ma.np = np;
+  ma.n = n;
+  ma.ts = a.ts;
+  ma.st = a.st;
+  ma.code = a.code;
+  ma.consts = a.consts;
+  for (int m = 0; m < 3; ++m) {
+    ma.off[m] = p.off[m];
+    ma.len[m] = p.len[m];
+  }
+  ma.cmin = p.cmin;
+  ma.cmax = p.cmax;
+  ma.within = p.within;
+  ma.ts_last = h.ts_last;
+  ma.ordinals = a.ordinals;
+  ma.obase = a.ordinal_base;
+  ma.perm = rows.perm;
+  ma.skey = rows.skey;
+  ma.kmin = h.kmin;
+  ma.kmax = h.kmax;
+  ma.sstr = rows.sstr;
+  ma.sid = sid;
+  ma.sa = p.stream[0];
+  ma.sb = p.stream[1];
+  ma.sc = p.stream[2];
+  ma.evt = (const int64_t*)carry.rows;
+  ma.ne = ne;
+  ma.cw = cw;
+  ma.parts = (const int64_t*)carry.parts;
+  ma.ncp = ncp;
+  ma.res = (int32_t*)sc.take((size_t)total * 4);
+  ma.kept = (int32_t*)sc.take((size_t)total * 4);
+  ma.mid = (int32_t*)sc.take((size_t)total * 4 * mw);
+  ma.eflag = (uint8_t*)sc.take((size_t)(ne + n));
+  uint32_t* counts = (uint32_t*)sc.take((size_t)(rtiles + 1) * 4);
+  uint32_t* kcounts = (uint32_t*)sc.take((size_t)(rtiles + 1) * 4);
+  SM_HIP(hipMemsetAsync(ma.eflag, 0, (size_t)(ne + n), s));
+  // rows that are not read have no lane: their entries are "none"
+  if (np < n) {
+    SM_HIP(hipMemsetD32Async((hipDeviceptr_t)(ma.res + ncp), (int)kSeqNone, (size_t)n, s));
+    SM_HIP(hipMemsetD32Async((hipDeviceptr_t)(ma.kept + ncp), (int)kSeqNone, (size_t)n, s));
+  }
+  const dim3 lgrid((unsigned)((ncp + np + kSeqTile - 1) / kSeqTile)), block(kSeqBlock);
+  if (wide) hipLaunchKernelGGL(pcnt_link_kernel<uint64_t>, lgrid, block, 0, s, ma);
+  else hipLaunchKernelGGL(pcnt_link_kernel<uint32_t>, lgrid, block, 0, s, ma);
+  b.mark("pcnt_link");
+  b.event(2);
+
+  // ---- the three counts: tuples, partials that stay, and the events they hold
+  const dim3 rgrid((unsigned)rtiles);
+  hipLaunchKernelGGL(seq_count_kernel, rgrid, block, 0, s, (const int32_t*)ma.res, total, counts);
+  hipLaunchKernelGGL(seq_count_kernel, rgrid, block, 0, s, (const int32_t*)ma.kept, total, kcounts);
+  b.mark(L.count);
+  exclusive_scan_u32(counts, (size_t)rtiles, sc, s, o.ctl + 1);
+  exclusive_scan_u32(kcounts, (size_t)rtiles, sc, s, npart);
+  b.mark(L.scan);
+  MPatKCand ca{};
+  ca.s = src;
+  ca.evt = ma.evt;
+  ca.ne = ne;
+  ca.cw = cw;
+  ca.eflag = ma.eflag;
+  ca.cand = o.cand;
+  ca.cand_n = o.ctl;
+  hipLaunchKernelGGL(mpatk_cand_kernel, seq_grid(ne + n, kSeqBlock), block, 0, s, ca);
+  b.mark(L.keep);
+  uint32_t hpart = 0;
+  SM_HIP(hipMemcpyAsync(&hpart, npart, 4, hipMemcpyDeviceToHost, s));
+  int64_t ncand;
+  const int64_t m = read_counts(b, o, tuples_cap, L, &ncand);
+  const int64_t pk = hpart;
+  // the cap on the open partials, which no window bounds: pcnt_carry_cap (fastpath.h), and the tuples' sort, the new partial table and the carry build
+  // must fit the scratch, now that the counts are known: still nothing is changed (per tuple: n + 2 words, two 64-bit
+  // sort keys, two indices and a histogram word per 4 tuples)
+  if (pk > pcnt_carry_cap(n, p.cmax, cw) ||
+      sc.used + (size_t)m * (4 * tw + 25) + (size_t)pk * pw * 8 + hist + 8192 > sc.cap ||
+      o.keep + (size_t)ncand * (size_t)(8 * cw + 44) + hist + 4096 > sc.cap)
+    return b.leave(FAST_OUTSIDE);
+
+  PCntOut oa{};
+  oa.s = src;
+  oa.total = total;
+  oa.ncp = ncp;
+  oa.mid = ma.mid;
+  oa.cmin = p.cmin;
+  oa.cmax = p.cmax;
+  oa.evt = ma.evt;
+  oa.cw = cw;
+  oa.parts = ma.parts;
+  // ---- the tuples in order of e1 (carried partials in their order, then row order), then one stable sort by (e3, p):
+  // e3 is always a batch row, over the bits of the largest relative ordinal; p may be a carried event, sign-flipped
+  if (m > 0) {
+    uint32_t* tup = (uint32_t*)sc.take((size_t)m * 4 * tw);
+    uint64_t* key = (uint64_t*)sc.take((size_t)m * 8);
+    uint64_t* key2 = (uint64_t*)sc.take((size_t)m * 8);
+    uint32_t* idx = (uint32_t*)sc.take((size_t)m * 4);
+    uint32_t* idx2 = (uint32_t*)sc.take((size_t)m * 4);
+    oa.flags = ma.res;
+    oa.offsets = counts;
+    oa.tuples = tup;
+    oa.key = key;
+    oa.idx = idx;
+    hipLaunchKernelGGL(pcnt_emit_kernel, rgrid, block, 0, s, oa);
+    b.mark(L.emit);
+    if (sort_pairs(true, key, key2, idx, idx2, m, 32 + std::max(1, bits_of((uint64_t)h.omax)), b)) std::swap(idx, idx2);
+    hipLaunchKernelGGL(mpatk_tuples_kernel, seq_grid(m, kSeqBlock), block, 0, s, (const uint32_t*)tup, tw,
+                       (const uint32_t*)idx, m, tuples_out);
+    b.mark("pcnt_order");
+  }
+  // ---- the partials that stay (the old ones are read until here), then their events
+  if (pk > 0) {
+    int64_t* pout = (int64_t*)sc.take((size_t)pk * pw * 8);
+    oa.flags = ma.kept;
+    oa.offsets = kcounts;
+    oa.parts_out = pout;
+    hipLaunchKernelGGL(pcnt_parts_kernel, rgrid, block, 0, s, oa);
+    carry.reserve_parts(pk, pw, s);
+    SM_HIP(hipMemcpyAsync(carry.parts, pout, (size_t)pk * pw * 8, hipMemcpyDeviceToDevice, s));
+    b.mark("pcnt_parts");
+  }
+  carry.pn = pk;
+  carry.pw = pw;
+  return carry_out(b, a, o, ncand, nattr, h.ts_last, carry, fs, 14, L, m, false, sid);
 }
 
 }  // namespace sm

@@ -1284,18 +1284,34 @@ __global__ void pair_project_kernel(const uint32_t* __restrict__ pairs, int64_t 
 // The arity-k sibling (the adjacent-run closed form's k-tuples, 3 <= k <= 8): slot s of output t is the event
 // tuples[k t + s]; any member but the last may be a carried row. kLogic: the logical pair's triples (e1, e2, e3), word w
 // holding slot lslot[w]; a word 0x80000000 is a member `or` left unbound, whose attributes read as null; the timestamp is
-// that of the later of e2 / e3, the completing member (always a batch row).
-template <bool kLogic>
+// that of the later of e2 / e3, the completing member (always a batch row). kMode 2: the count pattern's tuples
+// (e1, e2[0] .. e2[n-1], e3), k = n + 2 words: slot 1 at index i >= 0 is word 1 + i, at index CURRENT (e2[last]) the last
+// bound hit slot; a word 0x80000000 is a hit slot that is not bound, whose attributes read as null.
+template <int kMode>
 struct TupleLoader {
+  static constexpr bool kLogic = kMode == 1, kCount = kMode == 2;
   const NfaStream* st;
   int64_t r[8];        // batch rows
   const int64_t* c[8]; // carry rows, or nullptr
   int k;
-  uint32_t absent;     // kLogic: the slots `or` left unbound
+  uint32_t absent;     // kLogic: the slots `or` left unbound; kCount: the words of hit slots that are not bound
   __device__ StackVal var(const Instr& in) const {
     if (in.op == OP_COL) return col_value(st, in.a, r[k - 1]);
-    const int s = in.a < 0 ? 0 : in.a >= k ? k - 1 : in.a;
-    if (kLogic && ((absent >> s) & 1u)) {
+    int s = in.a < 0 ? 0 : in.a >= k ? k - 1 : in.a;
+    if (kCount) {
+      if (in.a <= 0) {
+        s = 0;
+      } else if (in.a >= 2) {
+        s = k - 1;
+      } else if (in.b >= 0) {
+        s = in.b < k - 2 ? 1 + in.b : -1;
+      } else {  // e2[last]
+        s = -1;
+        for (int w = k - 2; w >= 1 && s < 0; --w)
+          if (!((absent >> w) & 1u)) s = w;
+      }
+    }
+    if (kCount ? s < 0 || ((absent >> s) & 1u) : kLogic && ((absent >> s) & 1u)) {
       StackVal v;
       v.i = 0;
       v.d = 0;
@@ -1311,7 +1327,7 @@ struct TupleLoader {
   }
 };
 
-template <bool kLogic>
+template <int kMode>
 __global__ void tuple_project_kernel(const uint32_t* __restrict__ tuples, int64_t m, int arity,
                                      const NfaStream* __restrict__ st, const int64_t* __restrict__ ord, int64_t n,
                                      int64_t base, const int64_t* __restrict__ ts, const int64_t* __restrict__ crow,
@@ -1325,7 +1341,8 @@ __global__ void tuple_project_kernel(const uint32_t* __restrict__ tuples, int64_
   const Instr* code = (const Instr*)(blob + q->off_code);
   const DVal* consts = (const DVal*)(blob + q->off_const);
   const int32_t* sel = (const int32_t*)(blob + q->off_sel);
-  TupleLoader<kLogic> ld;
+  constexpr bool kLogic = kMode == 1, kCount = kMode == 2;
+  TupleLoader<kMode> ld;
   ld.st = st;
   ld.k = arity;
   ld.absent = 0;
@@ -1337,7 +1354,7 @@ __global__ void tuple_project_kernel(const uint32_t* __restrict__ tuples, int64_
     if (w >= arity) continue;
     const int s = !kLogic || w == 0 ? w : w == 1 ? lslot1 : lslot2;
     const uint32_t e = tuples[t * arity + w];
-    if (kLogic && e == 0x80000000u) {
+    if ((kLogic || kCount) && e == 0x80000000u) {
       ld.absent |= 1u << s;
     } else if ((int32_t)e < 0 && nc > 0) {  // a carried member: its row in the previous carry, by ordinal
       const uint32_t want = (uint32_t)((int32_t)e + 0x80000000ll);
@@ -1396,16 +1413,19 @@ void pair_project(const uint32_t* pairs, int64_t m, const NfaStream* st_dev, con
                   int64_t base, const int64_t* ts, const int64_t* prev_carry, int64_t nc, int cw, const char* blob_dev,
                   DVal* out, int64_t* ts_out, Scratch& sc, hipStream_t s, bool rows, int64_t* words,
                   uint8_t* nulls, const uint32_t* carry_keys, const uint32_t* carry_idx, bool sync, int arity,
-                  const int* logic_slot) {
+                  const int* logic_slot, bool count) {
   if (m <= 0) return;
   const size_t mark = sc.used;
   const uint32_t *ck = carry_keys, *ci = carry_idx;
   if (nc > 0 && !rows && !ck) pair_project_carry_order(prev_carry, nc, cw, base, sc, s, &ck, &ci);
-  if (logic_slot && arity == 3 && !rows)
-    hipLaunchKernelGGL(tuple_project_kernel<true>, grid_of(m), dim3(256), 0, s, pairs, m, arity, st_dev, ord, n, base, ts,
+  if (count && arity > 2 && !rows)
+    hipLaunchKernelGGL(tuple_project_kernel<2>, grid_of(m), dim3(256), 0, s, pairs, m, arity, st_dev, ord, n, base, ts,
+                       prev_carry, cw, ck, ci, nc, blob_dev, out, ts_out, words, nulls, 0, 0);
+  else if (logic_slot && arity == 3 && !rows)
+    hipLaunchKernelGGL(tuple_project_kernel<1>, grid_of(m), dim3(256), 0, s, pairs, m, arity, st_dev, ord, n, base, ts,
                        prev_carry, cw, ck, ci, nc, blob_dev, out, ts_out, words, nulls, logic_slot[1], logic_slot[2]);
   else if (arity > 2 && !rows)
-    hipLaunchKernelGGL(tuple_project_kernel<false>, grid_of(m), dim3(256), 0, s, pairs, m, arity, st_dev, ord, n, base, ts,
+    hipLaunchKernelGGL(tuple_project_kernel<0>, grid_of(m), dim3(256), 0, s, pairs, m, arity, st_dev, ord, n, base, ts,
                        prev_carry, cw, ck, ci, nc, blob_dev, out, ts_out, words, nulls, 0, 0);
   else
     hipLaunchKernelGGL(pair_project_kernel, grid_of(m), dim3(256), 0, s, pairs, m, st_dev, ord, n, base, ts, prev_carry,

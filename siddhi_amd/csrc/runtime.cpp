@@ -134,6 +134,8 @@ struct DevOut {
   int arity = 2;        // uint32 words per tuple of hp (a filter's rows: 1)
   bool logic = false;   // the logical pair's triples (e1, e2, e3): the trigger is the later of e2 / e3, and a member
                         // that `or` left unbound is the word 0x80000000
+  bool count = false;   // the count pattern's tuples (e1, e2[0] .. e2[n-1], e3): the trigger is e3, the last word, and
+                        // a hit slot that is not bound is the word 0x80000000
   // the trigger of output k, relative to base: its last event
   uint32_t trigger(size_t k) const {
     const uint32_t* tp = hp + (size_t)arity * k;
@@ -501,6 +503,21 @@ bool logic_progs_ok(const CompiledQuery& cq) {
       if (in.op != OP_VAR) continue;
       if (!(in.b == 0 || in.b == -1)) return false;
       if (!(in.a == 0 || (m > 0 && in.a == cq.fast_logic_slot[m]))) return false;
+    }
+  return true;
+}
+
+// The count pattern (fast_pat_count): c1 reads slot 0, c2 slot 0 and the current event of slot 1, c3 slot 0 and slot 2;
+// the same check otherwise.
+bool count_progs_ok(const CompiledQuery& cq) {
+  const Instr* code = (const Instr*)(cq.blob.data() + cq.hdr.off_code);
+  for (int m = 0; m < 3; ++m)
+    for (int i = 0; i < cq.fast_count_len[m]; ++i) {
+      const Instr& in = code[cq.fast_count_off[m] + i];
+      if (in.op == OP_TS || in.op == OP_COL) return false;
+      if (in.op != OP_VAR) continue;
+      if (in.a == 0 ? !(in.b == 0 || in.b == -1) : in.a != m || (m == 1 ? in.b != -1 : !(in.b == 0 || in.b == -1)))
+        return false;
     }
   return true;
 }
@@ -1288,7 +1305,9 @@ void read_outputs(sm_app* a, int qidx, const void* dev, int64_t n, std::vector<H
     const int64_t* rf = (const int64_t*)(b + sizeof(OutRec) + cq.hdr.nsel * sizeof(DVal));
     h.refs = rf;
     h.nrefs = cq.hdr.nrefs_vis;
-    if (cq.fast_seq_k || cq.fast_seq_ms || cq.fast_pat_k) {  // k hidden refs: the match's events in slot order
+    if (cq.fast_seq_k || cq.fast_seq_ms || cq.fast_pat_k || cq.fast_pat_count) {  // k hidden refs: the match's events in
+                                                                                // slot order (the count pattern: e1, the
+                                                                                // n hit slots, -1 where not bound, e3)
       h.tuple = rf + cq.hdr.nrefs_vis;
       h.e1 = h.tuple[0];
       h.e2 = h.tuple[cq.match_arity() - 1];
@@ -1585,7 +1604,7 @@ size_t batch_scratch(const sm_app* a, int64_t N) {
   int64_t lane_words = 0;
   for (auto& q : a->queries)
     if (q->cq.hdr.kind != 0) lane_words = std::max<int64_t>(lane_words, LaneEv::words(q->cq.hdr.node_words));
-  return (size_t)N * (100 + 8 * (size_t)lane_words) + (64 << 20);
+  return (size_t)N * (100 + 8 * (size_t)lane_words) + kBatchScratchSlack;
 }
 
 // The outputs of an NFA run over a device batch (the first nc positions replayed carried rows) as the closed form
@@ -1609,8 +1628,9 @@ void nfa_outs_to_device(sm_app* a, QueryRt& q, std::vector<HostOut>& outs, int64
     if (outs[k].r.pos < nc || outs[k].e1 < 0 || outs[k].e2 < 0 || (ar > 2 && !outs[k].tuple))
       throw std::runtime_error("query '" + q.cq.name + "': internal error in the hand-over of carried partials");
     if (ar > 2) {
-      for (size_t m = 0; m < ar; ++m)  // (an unbound member of the logical `or`: the null word)
-        pairs[ar * k + m] = q.cq.fast_pat_logic && outs[k].tuple[m] < 0 ? 0x80000000u
+      for (size_t m = 0; m < ar; ++m)  // (an unbound member of the logical `or`, a hit slot of the count pattern that
+                                       // is not bound: the null word)
+        pairs[ar * k + m] = (q.cq.fast_pat_logic || q.cq.fast_pat_count) && outs[k].tuple[m] < 0 ? 0x80000000u
                                                                         : (uint32_t)(outs[k].tuple[m] - ordinal_base);
     } else if (ar == 1) {  // the timeout: e1 alone
       pairs[k] = (uint32_t)(outs[k].e1 - ordinal_base);
@@ -1761,7 +1781,16 @@ int64_t nfa_device_batch(sm_app* a, int qi, int s, size_t n, const int64_t* d_ts
 // would hold an earlier one, which is then carried and replayed in front of it; A is neither B nor C, so no replayed
 // member opens a partial; nothing is emitted, since a partial holding both members has left the carry. `or`: the
 // events are e1 rows only; with A = B or A = C a replayed later row did not pass c2 / c3 against a carried earlier
-// one of its key, or that one would have matched and left the carry (path 12's argument). The playback
+// one of its key, or that one would have matched and left the carry (path 12's argument). And the count pattern
+// (fast_pat_count, path 14): the events are the e1 rows and the hits of the open partials. Replayed in (key, ordinal)
+// order every held event re-binds what it bound, in the same order and with the same clocks: a hit row passes c2 against
+// exactly the carried e1 rows in front of it that it passed before, and one of those that did not bind it then was full,
+// and is full again, since its n hits lie in front of the row and are replayed first; a bind sets the partial's clock to
+// the hit's own event time, as it did. The events that are not held had no effect on a surviving partial: a B row that
+// failed c2 or met a full partial, a C row that met a partial below m hits or failed c3 inside the window. A, B and C
+// are pairwise different, so no replayed member opens a partial or is bound as another element's; nothing is emitted,
+// since no C row is among them. A partial the carry dropped with n hits and its clock run out is not replayed: its next
+// C row would have killed it. The playback
 // clock is left alone, as in nfa_device_batch. The caller's event-index arrays (d_ev_*, d_adv_*) are overwritten.
 void mseq_replay_carry(sm_app* a, int qi, hipStream_t hs) {
   QueryRt& q = *a->queries[qi];
@@ -1971,7 +2000,7 @@ void device_outputs(sm_app* a, int qi, hipStream_t hs, std::vector<DevOut>& outs
     pair_project((const uint32_t*)q.dev_pairs.p + ar * k0, c, (const NfaStream*)q.proj_desc_dev.p,
                  q.proj_ord, q.proj_n, q.proj_base, q.proj_ts, (const int64_t*)q.prev_carry.p, q.prev_carry_n,
                  q.prev_carry_w, (const char*)q.blob.p, compact ? nullptr : (DVal*)dvals, dts, a->sc, hs, rows, dw, dn,
-                 ck, ci, !defer, ar, cq.fast_pat_logic ? cq.fast_logic_slot : nullptr);
+                 ck, ci, !defer, ar, cq.fast_pat_logic ? cq.fast_logic_slot : nullptr, cq.fast_pat_count != 0);
     if (compact) {
       SM_HIP(hipMemcpyAsync(hvals + (size_t)k0 * ns * 8, dw, (size_t)c * ns * 8, hipMemcpyDeviceToHost, hs));
       SM_HIP(hipMemcpyAsync(hvals + (size_t)m * ns * 8 + k0, dn, (size_t)c, hipMemcpyDeviceToHost, hs));
@@ -1989,6 +2018,7 @@ void device_outputs(sm_app* a, int qi, hipStream_t hs, std::vector<DevOut>& outs
   if (!defer) SM_HIP(hipStreamSynchronize(hs));
   DevOut d{qi, m, hp, compact ? nullptr : (const DVal*)hvals, hts, rows, q.proj_base, ar};
   d.logic = cq.fast_pat_logic != 0;
+  d.count = cq.fast_pat_count != 0;
   if (compact) {
     d.hw = (const int64_t*)hvals;
     d.hn = (const uint8_t*)(hvals + (size_t)m * ns * 8);
@@ -2035,6 +2065,16 @@ void materialize(sm_app* a, const DevOut& d, std::vector<HostOut>& outs) {
           const int sl = rslots[2 * r];
           const uint32_t w = tp[sl == 0 ? 0 : sl == cq.fast_logic_slot[1] ? 1 : 2];
           rf[r] = w == 0x80000000u ? -1 : d.base + (int32_t)w;
+          continue;
+        }
+        if (d.count) {  // (e1, the hit slots, e3): slot 1 at an index, or at CURRENT the last bound hit; an unbound
+                        // slot has no ordinal
+          const int sl = rslots[2 * r], ix = rslots[2 * r + 1];
+          int w = sl == 0 ? 0 : sl == 2 ? d.arity - 1 : ix >= 0 ? (ix < d.arity - 2 ? 1 + ix : -1) : -1;
+          if (sl == 1 && ix < 0)
+            for (int x = d.arity - 2; x >= 1 && w < 0; --x)
+              if (tp[x] != 0x80000000u) w = x;
+          rf[r] = w < 0 || tp[w] == 0x80000000u ? -1 : d.base + (int32_t)tp[w];
           continue;
         }
         rf[r] = d.arity > 2 ? d.base + (int32_t)tp[rslots[2 * r]] : rslots[2 * r] == 0 ? e1 : e2;
@@ -2924,7 +2964,9 @@ void device_batch_stream(sm_app* a, int s, size_t n, const int64_t* d_ts, const 
 // the batch has succeeded a->clock advances to the largest event time of the feed's rows, as path 11 advances it, so
 // that a later hand-over starts from the right clock) or the logical pair `every e1=A -> e2=B and|or e3=C within T`
 // (CompiledQuery::fast_pat_logic, fast_pat_logic, path 13: (e1, e2, e3) triples in dev_pairs, carried members projected
-// from prev_carry, the carried events, as path 10's). `nst` are the host copies of the batch's stream
+// from prev_carry, the carried events, as path 10's) or the count pattern `every e1=A -> e2=B<m:n> -> e3=C within T`
+// (CompiledQuery::fast_pat_count, fast_pat_count, path 14: tuples (e1, e2[0] .. e2[n-1], e3) in dev_pairs, likewise).
+// `nst` are the host copies of the batch's stream
 // descriptors, already uploaded to d_streams. Returns the number of matches (the projection state set as in
 // device_batch_stream; the outputs that have consumers appended to draw), or FAST_OUTSIDE / FAST_NON_MONOTONE with
 // nothing changed.
@@ -2936,7 +2978,8 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
   const bool pat = cq.fast_pat_ms;
   const bool nand = cq.fast_pat_nand;
   const bool logic = cq.fast_pat_logic != 0;
-  const int s0 = logic ? cq.fast_logic_stream[0] : nand ? cq.fast_nand_stream[0] : pat ? cq.fast_pat_stream[0] : cq.streams.at(0);
+  const bool count = cq.fast_pat_count != 0;
+  const int s0 = count ? cq.fast_count_stream[0] : logic ? cq.fast_logic_stream[0] : nand ? cq.fast_nand_stream[0] : pat ? cq.fast_pat_stream[0] : cq.streams.at(0);
   const NfaStream& d = nst[s0];
   const char* blob = (const char*)q.blob.p;
   a->sc.used = 0;
@@ -2954,9 +2997,20 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
   MPatKPlan kp;
   PNandPlan np;
   PLogPlan lp;
+  PCntPlan cp;
   const int patk = cq.fast_pat_k;
   std::vector<int> read;  // the streams the query reads
-  if (logic) {
+  if (count) {
+    cp.cmin = cq.fast_count_min;
+    cp.cmax = cq.fast_pat_count;
+    for (int m = 0; m < 3; ++m) {
+      cp.stream[m] = cq.fast_count_stream[m];
+      cp.off[m] = cq.fast_count_off[m];
+      cp.len[m] = cq.fast_count_len[m];
+    }
+    cp.within = cq.fast_count_within;
+    read.assign(cp.stream, cp.stream + 3);
+  } else if (logic) {
     lp.land = cq.fast_pat_logic == 1;
     for (int m = 0; m < 3; ++m) {
       lp.stream[m] = cq.fast_logic_stream[m];
@@ -3002,12 +3056,12 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
     }
     read = cq.streams;
   }
-  MSeqKeys& keys = logic ? static_cast<MSeqKeys&>(lp) : nand ? static_cast<MSeqKeys&>(np) : patk ? static_cast<MSeqKeys&>(kp) : pat ? static_cast<MSeqKeys&>(pp) : sp;
+  MSeqKeys& keys = count ? static_cast<MSeqKeys&>(cp) : logic ? static_cast<MSeqKeys&>(lp) : nand ? static_cast<MSeqKeys&>(np) : patk ? static_cast<MSeqKeys&>(kp) : pat ? static_cast<MSeqKeys&>(pp) : sp;
   keys.keyed = cq.partition >= 0;
   for (int s : read) {  // every read stream's own key attribute
     keys.read |= 1ull << s;
     if (!keys.keyed) continue;
-    const int c = (logic ? cq.fast_logic_keycol : nand ? cq.fast_nand_keycol : patk ? cq.fast_patk_keycol : pat ? cq.fast_pat_keycol : cq.fast_ms_keycol).at(s);
+    const int c = (count ? cq.fast_count_keycol : logic ? cq.fast_logic_keycol : nand ? cq.fast_nand_keycol : patk ? cq.fast_patk_keycol : pat ? cq.fast_pat_keycol : cq.fast_ms_keycol).at(s);
     keys.kcol[s] = d_cols[c];
     if (d.types[c] == T_LONG) keys.wide |= 1ull << s;
   }
@@ -3021,9 +3075,9 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
   };
   // a sequence: k words per match, at most one match per event; the pattern: (e1, e2) per match, at most one per partial
   // the k-state pattern: k words per match, at most one per partial
-  // the logical pair: three words per match, at most one per partial
-  const int64_t cap = patk || logic ? (int64_t)n + q.carry.pn : pat || nand ? (int64_t)n + q.carry.n : (int64_t)n;
-  q.dev_pairs.ensure(std::max<size_t>(logic ? (size_t)cap * 12 : patk ? (size_t)cap * 4 * (size_t)patk : pat || nand ? (size_t)cap * 8 : n * 4 * (size_t)sp.k, 16));
+  // the logical pair: three words per match, at most one per partial; the count pattern: n + 2 words likewise
+  const int64_t cap = patk || logic || count ? (int64_t)n + q.carry.pn : pat || nand ? (int64_t)n + q.carry.n : (int64_t)n;
+  q.dev_pairs.ensure(std::max<size_t>(count ? (size_t)cap * 4 * (size_t)cq.match_arity() : logic ? (size_t)cap * 12 : patk ? (size_t)cap * 4 * (size_t)patk : pat || nand ? (size_t)cap * 8 : n * 4 * (size_t)sp.k, 16));
   FastTimings* tm = a->fast_timing ? &a->fast_tm : nullptr;
   // the logical absent: build_event_index's clock_out alone, the largest event time of the feed's rows (heartbeats and
   // unread rows included) or the clock before it. One reduction in front of the driver, in stream order; its value is
@@ -3035,6 +3089,8 @@ int64_t interleaved_device_events(sm_app* a, int qi, size_t n, const int32_t* d_
     a->sc.used = 0;  // (the driver's kernels follow the reduction on the stream)
   }
   auto closed = [&] {
+    if (count)
+      return fast_pat_count(fa, d_stream_idx, cp, d.nattr, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, cap, a->sc, hs, tm);
     if (logic)
       return fast_pat_logic(fa, d_stream_idx, lp, d.nattr, q.fast, q.carry, (uint32_t*)q.dev_pairs.p, cap, a->sc, hs, tm);
     if (nand)
@@ -3447,7 +3503,7 @@ void flush(sm_app* a) {
     for (size_t qi = 0; qi < a->queries.size(); ++qi) {
       QueryRt& q = *a->queries[qi];
       if (!(q.cq.fast_seq_ms || q.cq.fast_pat_ms || q.cq.fast_pat_k || q.cq.fast_absent || q.cq.fast_pat_nand ||
-            q.cq.fast_pat_logic) ||
+            q.cq.fast_pat_logic || q.cq.fast_pat_count) ||
           q.nfa_mode || q.nfa_used ||
           !q.carry.active)
         continue;
@@ -4026,9 +4082,11 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
     // And the timeout `every e1=A -> not B for W` (CompiledQuery::fast_absent, path 11).
     // And the logical absent `every e1=A -> not B and e3=C within T` (CompiledQuery::fast_pat_nand, path 12).
     // And the logical pair `every e1=A -> e2=B and|or e3=C within T` (CompiledQuery::fast_pat_logic, path 13).
+    // And the count pattern `every e1=A -> e2=B<m:n> -> e3=C within T` (CompiledQuery::fast_pat_count, path 14).
     if (a->queries.size() == 1 &&
         (a->queries[0]->cq.fast_seq_ms > 0 || a->queries[0]->cq.fast_pat_ms || a->queries[0]->cq.fast_pat_k > 0 ||
-         a->queries[0]->cq.fast_absent || a->queries[0]->cq.fast_pat_nand || a->queries[0]->cq.fast_pat_logic) &&
+         a->queries[0]->cq.fast_absent || a->queries[0]->cq.fast_pat_nand || a->queries[0]->cq.fast_pat_logic ||
+         a->queries[0]->cq.fast_pat_count) &&
         a->streams.size() <= 64)
       msq = a->queries[0].get();
     size_t need = batch_scratch(a, N);
@@ -4048,6 +4106,10 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
       // the k-state pattern: result, kept and k - 1 members per row and carried partial, a flag per event, k words and
       // two sort pairs per tuple, the new partials (fast_pat_k checks the last two once they are counted). The logical
       // pair: the same with k = 3 (three members per row; fast_pat_logic makes the same checks)
+      // The count pattern (k = n + 4, rows of n + 5 words) needs, per row and carried partial: res 4, kept 4, mid
+      // 4 (n + 1), the tuple 4 (n + 2), two 64-bit sort keys and two indices 24, a histogram word per 4 tuples 1, the new
+      // partial row 8 (n + 5) = 16 n + 85 bytes; the formula grants 16 n + 92 with k = n + 4: 4 (k + 1) covers res, kept
+      // and mid, 4 k the tuple, 16 the sort keys' first copy, 8 (k + 1) the partial row and the rest of the sort
       if (const size_t k = (size_t)msq->cq.carry_parts_k()) {
         const size_t pn = (size_t)msq->carry.pn;
         need += (n + pn) * (4 * (k + 1) + 4 * k + 16 + 8 * (k + 1)) + n + nc;
@@ -4076,6 +4138,7 @@ int sm_app_process_device_events(sm_app* a, size_t n, const int32_t* d_stream_id
             (pat ? run_progs_ok(cq, cq.fast_pat_off, cq.fast_pat_len, 2)
                  : cq.fast_pat_nand ? nand_progs_ok(cq)
                  : cq.fast_pat_logic ? logic_progs_ok(cq)
+                 : cq.fast_pat_count ? count_progs_ok(cq)
                  : cq.fast_absent ? run_progs_ok(cq, cq.fast_abs_off, cq.fast_abs_len, 2)
                  : cq.fast_pat_k ? run_progs_ok(cq, cq.fast_patk_off, cq.fast_patk_len, cq.fast_pat_k)
                                  : run_progs_ok(cq, cq.fast_ms_off, cq.fast_ms_len, cq.fast_seq_ms))) {
@@ -4419,6 +4482,16 @@ int sm_app_restore(sm_app* a, const uint8_t* buf, size_t len) {
           };
           for (int64_t c = 0; c < pn; ++c) {
             const int64_t* pr = rows.data() + c * pw;
+            if (const int nmax = q.cq.fast_pat_count) {
+              // the count pattern: [key, hits | in-e3 << 8, tlast, p, o1, hit ordinals]: hits <= n, the in-e3 bit
+              // what hits and m say, e1 and every hit present in the event table
+              const int64_t hits = pr[1] & 0xff;
+              bool ok = pr[1] >= 0 && hits <= nmax && (pr[1] >> 8) == (hits >= q.cq.fast_count_min ? 1 : 0) &&
+                        held(pr[0], pr[4]);
+              for (int64_t i = 0; ok && i < hits; ++i) ok = held(pr[0], pr[5 + i]);
+              if (!ok) throw std::runtime_error("CannotRestoreSiddhiAppStateException: bad carry");
+              continue;
+            }
             // the logical pair: state 1 holds e1, 2 and 3 hold e1 and one of e2 / e3; `or` has state 1 only
             const bool lg = q.cq.fast_pat_logic != 0;
             bool ok = pr[1] >= 1 && (lg ? pr[1] <= (q.cq.fast_pat_logic == 1 ? 3 : 1) : pr[1] < pk);
@@ -4664,6 +4737,29 @@ int sm_app_get_stat(sm_app* a, const char* key, double* out) {
         }
       throw sql::ValidationError("No query with name " + k.substr(12));
     }
+    // the open partials a closed form with a partial table carries, and (the count pattern) those of them below m
+    // hits, which no window ends
+    if (k.rfind("carry_partials:", 0) == 0 || k.rfind("carry_unclocked:", 0) == 0) {
+      const bool all = k[6] == 'p';
+      const std::string name = k.substr(all ? 15 : 16);
+      for (auto& q : a->queries)
+        if (q->cq.name == name) {
+          *out = 0;
+          if (q->nfa_mode || !q->cq.carry_parts_k() || q->carry.pn == 0) return;
+          if (all) {
+            *out = (double)q->carry.pn;
+            return;
+          }
+          if (!q->cq.fast_pat_count) return;
+          std::vector<int64_t> rows((size_t)q->carry.pn * q->carry.pw);
+          SM_HIP(hipMemcpy(rows.data(), q->carry.parts, rows.size() * 8, hipMemcpyDeviceToHost));
+          int64_t c = 0;
+          for (int64_t r = 0; r < q->carry.pn; ++r) c += (rows[(size_t)r * q->carry.pw + 1] & 0xff) < q->cq.fast_count_min;
+          *out = (double)c;
+          return;
+        }
+      throw sql::ValidationError("No query with name " + name);
+    }
     if (k.rfind("fast_path:", 0) == 0) {
       for (auto& q : a->queries)
         if (q->cq.name == k.substr(10)) {
@@ -4761,7 +4857,8 @@ int sm_app_device_project(sm_app* a, const char* query_name, sm_dval* d_values, 
     pair_project((const uint32_t*)q->dev_pairs.p, m, (const NfaStream*)q->proj_desc_dev.p, q->proj_ord, q->proj_n,
                  q->proj_base, q->proj_ts, (const int64_t*)q->prev_carry.p, q->prev_carry_n, q->prev_carry_w,
                  (const char*)q->blob.p, (DVal*)d_values, d_ts, a->sc, hs, q->cq.hdr.kind == 0, nullptr, nullptr, nullptr,
-                 nullptr, true, q->cq.match_arity(), q->cq.fast_pat_logic ? q->cq.fast_logic_slot : nullptr);
+                 nullptr, true, q->cq.match_arity(), q->cq.fast_pat_logic ? q->cq.fast_logic_slot : nullptr,
+                 q->cq.fast_pat_count != 0);
   });
 }
 

@@ -33,6 +33,10 @@ fast_timing. Each step starts from a fresh runtime state (option reset), as benc
                                                         # within 1 sec` on the same three-way stream index, and with
                                                         # --query logic_or its `or` form: fast_path 13
                                                         # (kernels/mpat_logic_dev.h); routes as for --query streams
+    python tools/seq_bench.py --query pattern_count ...     # the count pattern `every e1=A[c1] -> e2=B[c2]<2:4> ->
+                                                        # e3=C[c3] within 1 sec` on the same three-way stream index:
+                                                        # fast_path 14 (kernels/mpat_count_dev.h); routes as for --query
+                                                        # streams
 
 Step time is a host clock around work that ends in a device synchronise; a run without a GPU fails."""
 import argparse
@@ -76,9 +80,14 @@ QUERY_LOGIC = ("@info(name='q') from every e1=A[price>20] -> e2=B[price>e1.price
                "select e1.timestamp as i, e2.timestamp as j, e3.timestamp as l insert into OutputStream;")
 
 
+QUERY_COUNT = ("@info(name='q') from every e1=A[price>20] -> e2=B[price>e1.price]<2:4> -> e3=C[price<e1.price] within 1 sec "
+               "select e1.timestamp as i, e2[0].timestamp as j, e2[last].timestamp as k, e3.timestamp as l "
+               "insert into OutputStream;")
+
+
 STREAM_QUERIES = ("streams", "streams3", "pattern_streams", "pattern_chain", "absent", "absent_and", "logic_and",
-                  "logic_or")
-THREE_WAY = ("absent_and", "logic_and", "logic_or")  # queries on the three-way stream index
+                  "logic_or", "pattern_count")
+THREE_WAY = ("absent_and", "logic_and", "logic_or", "pattern_count")  # queries on the three-way stream index
 
 
 def apps(query, cancel_above="70"):
@@ -92,6 +101,9 @@ def apps(query, cancel_above="70"):
         q = QUERY_LOGIC.format(op=query[6:])
         return {"keyed": SCHEMA_ABC + "partition with (symbol of A, symbol of B, symbol of C) begin " + q + " end;",
                 "unkeyed": SCHEMA_ABC + q}
+    if query == "pattern_count":
+        return {"keyed": SCHEMA_ABC + "partition with (symbol of A, symbol of B, symbol of C) begin " + QUERY_COUNT + " end;",
+                "unkeyed": SCHEMA_ABC + QUERY_COUNT}
     if query in STREAM_QUERIES:
         q = {"streams": QUERY_AB, "streams3": QUERY_ABA, "pattern_streams": QUERY_PAT_AB,
              "pattern_chain": QUERY_PAT_ABA, "absent": QUERY_ABSENT}[query]
@@ -116,6 +128,8 @@ LABELS += ["pnand_facts", "pnand_pack", "pnand_sort", "pnand_next", "pnand_link"
            "pnand_order", "pnand_carry", "pnand_clock"]
 LABELS += ["plog_facts", "plog_pack", "plog_sort", "plog_link", "plog_count", "plog_scan", "plog_cand", "plog_emit",
            "plog_order", "plog_parts", "plog_carry"]
+LABELS += ["pcnt_facts", "pcnt_pack", "pcnt_sort", "pcnt_link", "pcnt_count", "pcnt_scan", "pcnt_cand", "pcnt_emit",
+           "pcnt_order", "pcnt_parts", "pcnt_carry"]
 
 
 def precompile(query, cancel_above):
@@ -154,11 +168,14 @@ def main():
     ap.add_argument("--route", choices=["closed", "nfa"], default="closed")
     ap.add_argument("--forms", default="keyed,unkeyed")
     ap.add_argument("--query", choices=["pair", "three", "streams", "streams3", "pattern_streams", "pattern_chain", "absent",
-                                        "absent_and", "logic_and", "logic_or"],
+                                        "absent_and", "logic_and", "logic_or", "pattern_count"],
                     default="pair")
     ap.add_argument("--cancel-above", default="70",
                     help="--query absent_and: the constant of c2 `not B[price>X]`; the outputs a large X adds are the "
                          "partials that the default cancels")
+    ap.add_argument("--heap-words", type=int, default=0,
+                    help="--route nfa: the NFA kernel's per-key partial-match arena (option heap_words); a count pattern's "
+                         "partials hold several events each and outgrow the default at 1e8 keyed events")
     ap.add_argument("--precompile", action="store_true")
     ap.add_argument("--precompile-one")
     a = ap.parse_args()
@@ -193,6 +210,8 @@ def main():
     torch.cuda.synchronize()
     for form in a.forms.split(","):
         opts = {"nfa_jit": 1} if a.route == "nfa" else {}
+        if a.route == "nfa" and a.heap_words:
+            opts["heap_words"] = a.heap_words
         app = ProductApp(apps(a.query, a.cancel_above)[form], **opts)
         app.set_collect(False)
         cols = [sym, price, price, ordinals]  # volume is not read: aliased
@@ -228,6 +247,9 @@ def main():
                 "build_id": build_id}
         if a.route == "closed":
             line["fast_path"] = int(app.get_stat("fast_path:q"))
+            if a.query == "pattern_count":  # the partials a step leaves open, and those below m hits (no window ends them)
+                line["carry_partials"] = int(app.get_stat("carry_partials:q"))
+                line["carry_unclocked"] = int(app.get_stat("carry_unclocked:q"))
             line["kernel_ms_median"] = {k: sorted(v)[len(v) // 2] for k, v in kern.items()}
         else:
             line["nfa_kernel"] = int(app.get_stat("nfa_kernel:q"))
